@@ -65,9 +65,18 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=210,
                     help="candidate frames per search over all GPUs (framesBatchSize; 210 = the reference README)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the ORB and BA legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures or checks: the "
+                         "sequential-schedule kernel pass (kernels_sequential, rooflines), the PCIe-inclusive "
+                         "steps, the BA / ORB / 4K / detector / geometry / pipeline legs with their oracle checks "
+                         "and the CPU baselines.  Without it: set-up, warm-up, the timed steps, the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float64 / "
+                         "float32): per-candidate keypoint and match counts, the selected candidate, the winner's "
+                         "keypoints, matches and descriptors (the next search's query set)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU-baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the ORB and BA legs")
     ap.add_argument("--overlap", default="desc_start", choices=["knn", "desc_end", "desc_start"],
                     help="where the next search's extraction may start (PipelinedScan overlap)")
     ap.add_argument("--sift-kernel", default="auto", choices=["auto", "colw", "band", "tab"],
@@ -75,7 +84,10 @@ def parse():
     ap.add_argument("--check-launch", action="store_true",
                     help="launch the ranks, shard the batch and print the rank layout, no GPU work "
                          "(gloo; the CPU test of the launcher)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch(args):
@@ -859,6 +871,31 @@ def cpu_baseline(frames, query, budget_s, threads=None, query_label=""):
                       f"ratio per frame, oracle C restatement (-O3, OpenMP {threads} threads)"}
 
 
+def dump_outputs(path, kp_all, mc_all, good, winner, desc):
+    """--dump-outputs: what the last timed step handed to its caller, one
+    DIR/<name>.npy each (float64; the descriptors float32, as the library
+    returns them).  The inputs are the seeded synthetic sequence, so two builds
+    run with the same arguments can be compared array for array.  Structured
+    records become one column per field, in the field order of the dtype."""
+    os.makedirs(path, exist_ok=True)
+
+    def columns(rec):
+        if rec is None:
+            return np.zeros((0, 0), np.float64)
+        return np.stack([rec[f].astype(np.float64) for f in rec.dtype.names], axis=1).reshape(len(rec), -1)
+
+    kps, mts = winner if winner is not None else (None, None)
+    arrays = {"keypoint_counts": np.asarray(kp_all, np.float64),      # FAST keypoints per candidate (global order)
+              "match_counts": np.asarray(mc_all, np.float64),         # ratio-test matches per candidate
+              "good": np.array([good], np.float64),                   # the selected candidate (-1: none)
+              "winner_keypoints": columns(kps),                       # x, y, size, angle, response, octave, class_id
+              "winner_matches": columns(mts)}                         # queryIdx, trainIdx, imgIdx, distance
+    if desc is not None:
+        arrays["winner_descriptors"] = np.asarray(desc, np.float32)   # handed over as the next query set
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     args = parse()
     launch(args)
@@ -926,6 +963,7 @@ def main():
     winner = [None]    # the last search's (keypoints, matches), on every rank
     pending = [None]   # the last search's winner transfer in flight (ShardedScan.winner_begin)
     kps_desc = [0]     # keypoints this rank described (accumulated per step)
+    picked = [None]    # the last search's winner as a global candidate index (--dump-outputs)
 
     cond = Conditions(featureExtractingThreshold=THRESHOLD, requiredExtractedPointsCount=0, frameBatchSize=B,
                       skipFramesFromBatchHead=0, useFirstFitInBatch=True,
@@ -956,6 +994,7 @@ def main():
         pending[0] = pscan.winner_begin(good, in_batch, dc_all, mc_all, nq)
         # hand-over: the winner's owner exports its descriptors (next broadcast root)
         owner, nprev = pscan.advance(good, in_batch, dc_all, prev, owner, nprev)
+        picked[0] = int(in_batch[good]) if good >= 0 else None
         return kp_all, mc_all, good
 
     def drain():
@@ -974,7 +1013,8 @@ def main():
         drain()
         return out
 
-    kp_all, mc_all, good = run(args.warmup)
+    if args.warmup:
+        run(args.warmup)
     ops[0] = 0.0
     kps_desc[0] = 0
     for c in pscan.ctxs:
@@ -994,6 +1034,15 @@ def main():
         el = float(t.item())
     # work of the timed region only (the H2D leg below calls step() again)
     ops_timed, kps_timed = ops[0], kps_desc[0]
+
+    if args.dump_outputs and rank == 0:
+        # the last timed search's batch is still resident (the last search queues
+        # no next extraction): the winner's descriptors as a caller reads them,
+        # when this rank owns the winner
+        desc = None
+        if picked[0] is not None and picked[0] % world == rank:
+            desc = pscan.db.descriptors(picked[0] // world)
+        dump_outputs(args.dump_outputs, kp_all, mc_all, int(good), winner[0], desc)
 
     # kernel timings (HIP events on the launch stream, timed region only)
     import ctypes
@@ -1018,8 +1067,9 @@ def main():
     # for CUs that this search's descriptor tail frees, so their event times
     # include that wait: the per-family rooflines come from a short pass on the
     # sequential schedule (same kernels, same inputs) right after the timed region
+    # (--full: a run of its own)
     prof_seq, ops_seq, kps_seq, nseq = prof, ops_timed, kps_timed, args.steps
-    if pscan.overlap != "knn":
+    if args.full and pscan.overlap != "knn":
         pscan.overlap = "knn"
         ops[0], kps_desc[0] = 0.0, 0
         nseq = max(2, min(args.steps, 8))
@@ -1032,31 +1082,33 @@ def main():
             slamhip.lib().slam_profile_enable(c.handle, 0)
         pscan.overlap = args.overlap
 
-    # PCIe-inclusive rate (host-buffer boundary): the same steps with this rank's
-    # frames copied from pinned host memory inside the timed region (never `value`)
-    host_pinned = torch.from_numpy(host).pin_memory()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        frames.copy_(host_pinned, non_blocking=True)
-        torch.cuda.current_stream().synchronize()   # the library's streams read the frames next
-        run(1)
-    torch.cuda.synchronize()
-    el_h2d = time.perf_counter() - t1
-    if world > 1:
-        t = torch.tensor([el_h2d], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        el_h2d = float(t.item())
+    el_h2d = h2d_gbps = None
+    if args.full:
+        # PCIe-inclusive rate (host-buffer boundary): the same steps with this rank's
+        # frames copied from pinned host memory inside the timed region (never `value`)
+        host_pinned = torch.from_numpy(host).pin_memory()
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            frames.copy_(host_pinned, non_blocking=True)
+            torch.cuda.current_stream().synchronize()   # the library's streams read the frames next
+            run(1)
+        torch.cuda.synchronize()
+        el_h2d = time.perf_counter() - t1
+        if world > 1:
+            t = torch.tensor([el_h2d], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            el_h2d = float(t.item())
 
-    # the copy alone (pinned host -> HBM), to check the PCIe-inclusive number
-    torch.cuda.synchronize()
-    t2 = time.perf_counter()
-    for _ in range(3):
-        frames.copy_(host_pinned, non_blocking=True)
-    torch.cuda.synchronize()
-    h2d_gbps = 3 * host.nbytes / (time.perf_counter() - t2) / 1e9
+        # the copy alone (pinned host -> HBM), to check the PCIe-inclusive number
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        for _ in range(3):
+            frames.copy_(host_pinned, non_blocking=True)
+        torch.cuda.synchronize()
+        h2d_gbps = 3 * host.nbytes / (time.perf_counter() - t2) / 1e9
 
     nloc = len(mine)
     value = B * args.steps / el                             # global candidates over the max-over-ranks time
@@ -1101,7 +1153,7 @@ def main():
         r["avg_ms"] = pf["avg_ms"]
         return r
 
-    roofs = {name: roofline(name, pf, ops_seq, kps_seq) for name, pf in prof_seq.items()}
+    roofs = {name: roofline(name, pf, ops_seq, kps_seq) for name, pf in prof_seq.items()} if args.full else {}
     dom = max(prof_seq, key=lambda k: prof_seq[k]["ms_per_step"]) if prof_seq else None
     roof = None
     if dom is not None and dom in prof:
@@ -1126,10 +1178,10 @@ def main():
     # extract + match + BA over the same global batch (configs[3] at any rank
     # count): every rank joins (RCCL exchanges, BA solved on rank 0 and broadcast)
     wba = with_ba_leg(pscan, scan, frames, first, B, pad_to, slamhip.SIFT_FLANN, check=rank == 0) \
-        if not args.no_extra else None
+        if args.full and not args.no_extra else None
     # single-GPU legs (the N = 1 run): configs[2], configs[4]'s front end and BA
     # window, the BA windows alone, the detector, geometry, the whole pipeline
-    solo = not args.no_extra and world == 1
+    solo = args.full and not args.no_extra and world == 1
     orb = orb_leg(pscan, db, frames, first, B, pad_to, steps=max(2, args.steps // 2), warmup=1) if solo else None
     ba = ba_leg(ctx, check=True) if solo else None
     c2 = with_ba_leg(pscan, scan, frames, first, B, pad_to, slamhip.ORB_BF, check=False) if solo else None
@@ -1168,7 +1220,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # all host threads (the reported baseline) and one thread, same sample
             # a sample spread over the batch, against the query the timed steps used
             # (the last search's winner: candidate `good` is synthetic frame 1 + good)
@@ -1217,14 +1269,14 @@ def main():
             "final_reproj_rmse_searched_frames": (pipe210.get("ba_final_rmse") or [None])[-1] if pipe210 else None,
             # PCIe-inclusive (host-buffer boundary), serialized: step time + the
             # measured pinned H2D time of this rank's frames; never `value`
-            "value_incl_h2d": B / (el / args.steps + host.nbytes / (h2d_gbps * 1e9)),
-            "h2d_GBps": h2d_gbps, "value_h2d_loop": B * args.steps / el_h2d,
+            "value_incl_h2d": B / (el / args.steps + host.nbytes / (h2d_gbps * 1e9)) if args.full else None,
+            "h2d_GBps": h2d_gbps, "value_h2d_loop": B * args.steps / el_h2d if args.full else None,
             "config2_with_ba": c2,
             "orb": orb, "sift_4k": s4k, "ba_window": ba, "ba_window_w16_4k": ba16, "sift_detector": sdet,
             "triangulation": geom, "pipeline": pipe, "pipeline_b210": pipe210, "pipeline_b210_orb": pipe210_orb,
             "pipeline_b210_early_exit": pipe210_ee,
             "overlap": args.overlap, "kernels": prof, "kernels_sequential": prof_seq if prof_seq is not prof else None,
-            "roofline": roof, "rooflines": roofs, "cpu_baseline": cpu,
+            "roofline": roof, "rooflines": roofs if args.full else None, "cpu_baseline": cpu, "full": args.full,
         }
         if cpu:
             out["speedup_vs_cpu_baseline"] = value / cpu["value"]

@@ -11,10 +11,12 @@ for v in "$@"; do
     rc=$?
     echo "$v tests rc=$rc $(tail -1 $R/gpurun_out/svc_$v.log)"
     [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
-    timeout -k 10 120 python3 $R/bench.py --steps 20 --warmup 3 --no-extra --no-cpu-baseline > $R/gpurun_out/svc_$v.json 2>$R/gpurun_out/svc_$v.err || exit $?
+    OUT=${OUT:-$R/bench_out}
+    mkdir -p $OUT
+    timeout -k 10 120 python3 $R/bench.py --full --steps 20 --warmup 3 --no-extra --no-cpu-baseline > $OUT/svc_$v.json 2>$OUT/svc_$v.err || exit $?
     python3 -c "
 import json
-d = json.loads(open('$R/gpurun_out/svc_$v.json').read().strip().splitlines()[-1])
+d = json.loads(open('$OUT/svc_$v.json').read().strip().splitlines()[-1])
 k = d.get('kernels_sequential') or d['kernels']
 print('$v', 'step', round(d['ms_per_step'], 3), {n: round(x['avg_ms'], 4) for n, x in k.items()})"
 done

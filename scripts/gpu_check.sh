@@ -10,7 +10,9 @@ timeout -k 10 600 python -m pytest tests/test_gpu_parity.py -m gpu -q -p no:cach
 rc=$?
 echo "pytest exit $rc" >> gpurun_out/${TAG}_pytest.log
 if [ $rc -ge 2 ] && [ $rc -ne 5 ]; then echo "pytest rc=$rc: stopping"; exit $rc; fi
-timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
+OUT=${OUT:-bench_out}
+mkdir -p $OUT
+timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 rc2=$?
 echo "pytest $rc bench $rc2"
 exit $rc2

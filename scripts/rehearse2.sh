@@ -7,7 +7,7 @@ set -o pipefail
 N=${1:-4}
 mkdir -p gpurun_out
 SLAMHIP_DIST_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-    --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $N --steps 5 --warmup 2 --no-cpu-baseline \
+    --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $N --full --steps 5 --warmup 2 --no-cpu-baseline \
     > gpurun_out/rehearse$N.json 2> gpurun_out/rehearse$N.err || { echo "failed"; tail -20 gpurun_out/rehearse$N.err; exit 1; }
 grep '^{' gpurun_out/rehearse$N.json | python -c "
 import json,sys; d=json.loads(sys.stdin.read())

@@ -236,9 +236,11 @@ def test_orb_border_filter_in_place_order():
 def test_orb_pattern_table_matches_source():
     import subprocess
     import sys
-    subprocess.check_call([sys.executable, os.path.join(O.ORACLE_DIR, "gen_orb_pattern.py")]) \
-        if os.path.exists("/opt/conda/lib/python3.9/site-packages/skimage/feature/orb_descriptor_positions.txt") \
-        else pytest.skip("pattern source not present")
+    # the table itself is kept under tests/golden (256 x 4 offsets, scikit-image's
+    # orb_descriptor_positions.txt = OpenCV's bit_pattern_31_)
+    subprocess.check_call([sys.executable, os.path.join(O.ORACLE_DIR, "gen_orb_pattern.py"),
+                           os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                                        "orb_bit_pattern_31.npy")])
 
 
 def test_orb_descriptor_brute_force():
