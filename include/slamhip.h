@@ -13,6 +13,9 @@
  *   slam_matcher_type    getMatcherTypeIndex           featureMatchingCommon.h:19, featureMatchingCommon.cpp:13-21
  *   slam_select_good     findGoodFramesFromBatch* selection rule  batch.cpp:136-146 / :280-316
  *   slam_ba              bundleAdjustment              src/mainModule/bundleAdjustment/bundleAdjustment.h:50-54
+ *   slam_cluster_points  clusterizePoints              src/vizualization/delauney-triangulation/geomAdditionalFunc.cpp:105-163
+ *   slam_fit_plane       getBestFittingPlaneByPoints   src/vizualization/delauney-triangulation/bestFittingPlane.cpp:11-40
+ *   slam_project_to_plane projectPointOnPlane + makeMesh geomAdditionalFunc.cpp:20-32, bestFittingPlane.cpp:51-63
  *   slam_batch_*         the data-parallel candidate scan around them, batch.cpp:59-226
  *
  * Conventions
@@ -203,6 +206,49 @@ int slam_solve_pnp_ransac(slam_ctx* ctx, const float* obj, const float* img, int
  * src/mainModule/bundleAdjustment/bundleAdjustment.cpp:167,195
  * (convertDataForBA / convertDataFromBA).  Other n: SLAM_E_INVALID_ARG. */
 int slam_rodrigues(const double* src, int n, double* dst);
+
+/* ---- scene post-processing (src/vizualization, after slamMain / an onlyViz reload) ---- */
+/* clusterizePoints -- geomAdditionalFunc.cpp:105-163.  pts: n x 3 float (the
+ * Point3f the reference narrows to, main.cpp:61-64); colors: n x 3 uint8
+ * (Vec3b); max_distance / euclid_weight / color_weight: the config floats
+ * TriangleMaxDistance / TriangleEuclidDistanceWeight / TriangleColorDistance
+ * (widened to double as the reference does).  i and j are joined iff
+ * sqrt(|p_i - p_j|^2) * euclid_weight + norm(c_i, c_j) * color_weight <
+ * max_distance, in the reference's exact arithmetic; labels[i] = the smallest
+ * index of i's connected component, *n_components = their number.  The
+ * reference's comps are the label classes ordered by label (its order of
+ * discovery); it lists the members in DFS pre-order, which labels do not keep.
+ * n == 0: SLAM_OK, no launch.  More than ~16.7M points: SLAM_E_UNSUPPORTED. */
+int slam_cluster_points(slam_ctx* ctx, const float* pts /* n x 3 */, const uint8_t* colors /* n x 3 */,
+                        int n, float max_distance, float euclid_weight, float color_weight,
+                        int32_t* labels /* n */, int* n_components);
+/* the same on device buffers, queued on `stream` (NULL = the context stream)
+ * without a host wait; d_labels doubles as the union-find's parent array */
+int slam_cluster_points_dev(slam_ctx* ctx, void* stream, const float* d_pts, const uint8_t* d_colors, int n,
+                            float max_distance, float euclid_weight, float color_weight, int32_t* d_labels);
+/* counters of the context's last clustering call (waits for it): *pairs =
+ * n (n - 1) / 2, *exact_pairs = the pairs that passed the f32 reject and took
+ * the f64 path (scripts/scene_bench.py reports the fraction) */
+int slam_cluster_last_stats(slam_ctx* ctx, uint64_t* pairs, uint64_t* exact_pairs);
+
+/* getBestFittingPlaneByPoints -- bestFittingPlane.cpp:11-40.  centroid = the
+ * f64 mean of the points rounded to f32 (Point3f(mean(row)[0], ...)); normal =
+ * the unit eigenvector of the smallest eigenvalue of the centred points'
+ * second-moment matrix, signed so that its largest-magnitude component is
+ * positive.  (The reference reads its normal with at<double> out of a CV_32F
+ * SVD result -- garbage -- so this is its evident intent, DESIGN.md.)  The sums
+ * are deterministic: two calls agree bit for bit.  n < 1: SLAM_E_INVALID_ARG. */
+int slam_fit_plane(slam_ctx* ctx, const float* pts, int n, float* centroid /* 3 */, double* normal /* 3 */);
+/* the device part of slam_fit_plane: sum = sum of the points (f64), mean =
+ * sum / n, moments = {xx, xy, xz, yy, yz, zz} of the points minus the f64 mean */
+int slam_plane_moments(slam_ctx* ctx, const float* pts, int n, double* sum /* 3 */, double* mean /* 3 */,
+                       double* moments /* 6 */);
+/* projectPointOnPlane (geomAdditionalFunc.cpp:20-32) + makeMesh's flattening
+ * (bestFittingPlane.cpp:51-63) per point, bit for bit: out_xy[i] = the (x, z)
+ * of the projected, centred and rescaled point (Point2f), inf / NaN where the
+ * reference divides by zero. */
+int slam_project_to_plane(slam_ctx* ctx, const float* pts, int n, const float* centroid /* 3 */,
+                          const double* normal /* 3 */, float* out_xy /* n x 2 */);
 
 /* knnMatch(query, train, k = 2): idx/dist nq x 2 (idx -1 where missing). */
 int slam_knn2(slam_ctx* ctx, const void* q, int nq, const void* t, int nt,

@@ -231,8 +231,12 @@ struct slam_ctx {
 
     // full SIFT detector (siftdet.hip): Gaussian + DoG pyramid, candidates, keypoints
     slamhip::DevBuf sd_pyr, sd_cand, sd_kps, sd_kpc;   // sd_kpc: the refined keypoints, frame-major
-    // two-view geometry (geom.hip)
+    // two-view geometry (geom.hip); also the staged inputs of the scene calls (cluster.hip)
     slamhip::DevBuf geom;
+    // scene post-processing (cluster.hip): pair counters, then the plane fit's slots
+    slamhip::DevBuf cluster;
+    unsigned long long cluster_pairs_total = 0;   // n (n - 1) / 2 of the last clustering call
+    hipStream_t cluster_stats_stream = nullptr;   // ... and the stream it ran on
 
     // SIFT gather table for one (angle, size) (sift_tab.hip)
     slamhip::DevBuf sift_tab;

@@ -201,6 +201,27 @@ bool solvePnPRansac(const std::vector<Point3f>& objectPoints, const std::vector<
                     int iterationsCount = 100, float reprojectionError = 8.0f, double confidence = 0.99,
                     std::vector<int>* inliers = nullptr);
 
+// ---- scene post-processing (src/vizualization) ----------------------------------------
+struct Vec3b { uint8_t v[3] = {0, 0, 0}; };    // cv::Vec3b layout
+struct Vec3d { double v[3] = {0, 0, 0}; };     // cv::Vec3d layout
+
+// clusterizePoints(points, colors, comps) -- geomAdditionalFunc.cpp:105-163; reads
+// TriangleMaxDistance / TriangleEuclidDistanceWeight / TriangleColorDistance from
+// the global configService as the reference does.  comps come in the
+// reference's order (by smallest member); members ascend inside a component
+// (the reference lists them in DFS pre-order).
+void clusterizePoints(const std::vector<Point3f>& points, const std::vector<Vec3b>& colors,
+                      std::vector<std::vector<int>>& comps);
+
+// getBestFittingPlaneByPoints(points, centroid, normal) -- bestFittingPlane.cpp:11-40
+// (the evident intent: see include/slamhip.h, slam_fit_plane)
+void getBestFittingPlaneByPoints(const std::vector<Point3f>& points, Point3f& centroid, Vec3d& normal);
+
+// projectPointOnPlane + the flattening of makeMesh (bestFittingPlane.cpp:51-63)
+// for every point: the Point2f list handed to the triangulation
+void projectToPlane(const std::vector<Point3f>& points, const Point3f& centroid, const Vec3d& normal,
+                    std::vector<Point2f>& projected);
+
 std::array<double, 3> rodrigues(const std::array<double, 9>& R);
 std::array<double, 9> rodrigues(const std::array<double, 3>& r);
 

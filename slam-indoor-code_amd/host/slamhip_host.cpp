@@ -360,6 +360,56 @@ void reconstruct(const std::array<double, 9>& K, const std::array<double, 9>& R1
           &ctx);
 }
 
+void clusterizePoints(const std::vector<Point3f>& points, const std::vector<Vec3b>& colors,
+                      std::vector<std::vector<int>>& comps)
+{
+    if (points.size() != colors.size()) throw Error("clusterizePoints: points and colors differ in length");
+    Context& ctx = Context::thread_default();
+    // getValue<float> assigned to double (geomAdditionalFunc.cpp:114-117)
+    const float max = (float)configService.getValue<double>("TriangleMaxDistance");
+    const float dw = (float)configService.getValue<double>("TriangleEuclidDistanceWeight");
+    const float cw = (float)configService.getValue<double>("TriangleColorDistance");
+    const int n = (int)points.size();
+    std::vector<int32_t> labels(points.size());
+    int ncomp = 0;
+    check(slam_cluster_points(ctx.get(), reinterpret_cast<const float*>(points.data()),
+                              reinterpret_cast<const uint8_t*>(colors.data()), n, max, dw, cw, labels.data(), &ncomp),
+          &ctx);
+    // labels[i] = smallest member of i's component: the roots in index order are
+    // the reference's order of discovery
+    std::vector<int> slot(points.size(), -1);
+    comps.reserve(comps.size() + (size_t)ncomp);
+    const size_t base = comps.size();
+    for (int i = 0; i < n; i++)
+        if (labels[i] == i) {
+            slot[i] = (int)(comps.size() - base);
+            comps.emplace_back();
+        }
+    for (int i = 0; i < n; i++) comps[base + (size_t)slot[labels[i]]].push_back(i);
+}
+
+void getBestFittingPlaneByPoints(const std::vector<Point3f>& points, Point3f& centroid, Vec3d& normal)
+{
+    Context& ctx = Context::thread_default();
+    float c[3];
+    check(slam_fit_plane(ctx.get(), reinterpret_cast<const float*>(points.data()), (int)points.size(), c, normal.v),
+          &ctx);
+    centroid.x = c[0];
+    centroid.y = c[1];
+    centroid.z = c[2];
+}
+
+void projectToPlane(const std::vector<Point3f>& points, const Point3f& centroid, const Vec3d& normal,
+                    std::vector<Point2f>& projected)
+{
+    Context& ctx = Context::thread_default();
+    projected.assign(points.size(), Point2f{});
+    const float c[3] = {centroid.x, centroid.y, centroid.z};
+    check(slam_project_to_plane(ctx.get(), reinterpret_cast<const float*>(points.data()), (int)points.size(), c,
+                                normal.v, reinterpret_cast<float*>(projected.data())),
+          &ctx);
+}
+
 bool estimateTransformation(const std::vector<Point2f>& points1, const std::vector<Point2f>& points2,
                             const std::array<double, 9>& K, std::array<double, 9>& R, std::array<double, 3>& t,
                             std::vector<uint8_t>& chiralityMask)

@@ -53,6 +53,7 @@ class BASummary(ctypes.Structure):
 
 # exported symbols and their signatures: (restype, argtypes)
 _P, _I, _SZ, _D, _U64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_double, ctypes.c_uint64
+_F = ctypes.c_float
 SIGNATURES = {
     "slam_abi_version": (_I, []),
     "slam_device_count": (_I, []),
@@ -105,6 +106,12 @@ SIGNATURES = {
     "slam_synth_sequence": (_I, [_I, _I, _I, _I, _U64, _I, _P]),
     "slam_batch_fast": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "slam_synth_sequence_dev": (_I, [_P, _P, _I, _I, _I, _I, _U64, _I, _P]),
+    "slam_cluster_points": (_I, [_P, _P, _P, _I, _F, _F, _F, _P, _P]),
+    "slam_cluster_points_dev": (_I, [_P, _P, _P, _P, _I, _F, _F, _F, _P]),
+    "slam_cluster_last_stats": (_I, [_P, _P, _P]),
+    "slam_fit_plane": (_I, [_P, _P, _I, _P, _P]),
+    "slam_plane_moments": (_I, [_P, _P, _I, _P, _P, _P]),
+    "slam_project_to_plane": (_I, [_P, _P, _I, _P, _P, _P]),
 }
 
 _lib = None

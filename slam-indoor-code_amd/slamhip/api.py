@@ -451,6 +451,103 @@ def ba_rmse(summary):
     return math.sqrt(summary.initial_cost / summary.num_residuals), math.sqrt(summary.final_cost / summary.num_residuals)
 
 
+# ---- scene post-processing (src/vizualization) ---------------------------------------
+
+def cluster_params(config_or_params):
+    """(max, euclid weight, colour weight) as the reference reads them
+    (geomAdditionalFunc.cpp:114-117, getValue<float>): from a config object with
+    getValue, or a (max, euclid_weight, color_weight) triple.  Rounded to f32."""
+    g = getattr(config_or_params, "getValue", None)
+    if g is not None:
+        t = (g("TriangleMaxDistance"), g("TriangleEuclidDistanceWeight"), g("TriangleColorDistance"))
+    else:
+        t = tuple(config_or_params)
+        if len(t) != 3:
+            raise ValueError("params are (max_distance, euclid_weight, color_weight)")
+    return tuple(float(np.float32(v)) for v in t)
+
+
+def _cloud(points, colors):
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    c = np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+    if len(p) != len(c):
+        raise ValueError("points and colors differ in length")
+    return p, c
+
+
+def components_from_labels(labels):
+    """label classes as a list of int32 index arrays, ordered by label (= by
+    smallest member), members ascending"""
+    labels = np.asarray(labels, np.int32)
+    if len(labels) == 0:
+        return []
+    order = np.argsort(labels, kind="stable").astype(np.int32)
+    cuts = np.nonzero(np.diff(labels[order]))[0] + 1
+    return np.split(order, cuts)
+
+
+def clusterLabels(points, colors, config_or_params, ctx=None):
+    """slam_cluster_points: labels[i] = the smallest index of point i's component"""
+    c = _ctx(ctx)
+    p, col = _cloud(points, colors)
+    mx, dw, cw = cluster_params(config_or_params)
+    labels = np.zeros(max(len(p), 1), np.int32)
+    nc = ctypes.c_int(0)
+    check(lib().slam_cluster_points(c, ptr(p), ptr(col), len(p), mx, dw, cw, ptr(labels), ctypes.byref(nc)), c)
+    return labels[:len(p)].copy(), nc.value
+
+
+def clusterizePoints(points, colors, config_or_params, ctx=None):
+    """geomAdditionalFunc.cpp:105-163 clusterizePoints(): the connected
+    components of the graph that joins points i and j iff
+    distance(p_i, p_j) * TriangleEuclidDistanceWeight + norm(c_i, c_j) *
+    TriangleColorDistance < TriangleMaxDistance (points n x 3, narrowed to
+    Point3f; colors n x 3 uint8).  Returns comps: a list of int32 index arrays
+    ordered by smallest member, which is the reference's order of discovery.
+    Members ascend within each array; the reference lists them in DFS
+    pre-order, so only the order inside a component differs."""
+    labels, nc = clusterLabels(points, colors, config_or_params, ctx)
+    comps = components_from_labels(labels)
+    assert len(comps) == nc
+    return comps
+
+
+def planeMoments(points, ctx=None):
+    """slam_plane_moments: (sum[3], mean[3], {xx, xy, xz, yy, yz, zz} about the
+    f64 mean), the deterministic device sums behind getBestFittingPlaneByPoints"""
+    c = _ctx(ctx)
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    s, mean, mom = np.zeros(3), np.zeros(3), np.zeros(6)
+    check(lib().slam_plane_moments(c, ptr(p), len(p), ptr(s), ptr(mean), ptr(mom)), c)
+    return s, mean, mom
+
+
+def getBestFittingPlaneByPoints(points, ctx=None):
+    """bestFittingPlane.cpp:11-40: (centroid float32[3], normal float64[3]) of
+    the least-squares plane through points (n x 3, Point3f).  The normal is the
+    unit eigenvector of the smallest eigenvalue of the centred second-moment
+    matrix, its largest-magnitude component positive (the reference's own
+    normal is an at<double> read of a CV_32F matrix: DESIGN.md)."""
+    c = _ctx(ctx)
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    centroid, normal = np.zeros(3, np.float32), np.zeros(3, np.float64)
+    check(lib().slam_fit_plane(c, ptr(p), len(p), ptr(centroid), ptr(normal)), c)
+    return centroid, normal
+
+
+def projectToPlane(points, centroid, normal, ctx=None):
+    """projectPointOnPlane (geomAdditionalFunc.cpp:20-32) and makeMesh's
+    flattening (bestFittingPlane.cpp:51-63) for every point, bit for bit:
+    the n x 2 float32 (x, z) points the Delaunay step consumes."""
+    c = _ctx(ctx)
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    cen = np.ascontiguousarray(centroid, np.float32).reshape(3)
+    nrm = np.ascontiguousarray(normal, np.float64).reshape(3)
+    out = np.zeros((max(len(p), 1), 2), np.float32)
+    check(lib().slam_project_to_plane(c, ptr(p), len(p), ptr(cen), ptr(nrm), ptr(out)), c)
+    return out[:len(p)].copy()
+
+
 SYNTH_DRIFT, SYNTH_STEADY = 0, 1
 
 
