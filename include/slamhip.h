@@ -16,6 +16,8 @@
  *   slam_cluster_points  clusterizePoints              src/vizualization/delauney-triangulation/geomAdditionalFunc.cpp:105-163
  *   slam_fit_plane       getBestFittingPlaneByPoints   src/vizualization/delauney-triangulation/bestFittingPlane.cpp:11-40
  *   slam_project_to_plane projectPointOnPlane + makeMesh geomAdditionalFunc.cpp:20-32, bestFittingPlane.cpp:51-63
+ *   slam_delaunay_2d     builtInTriangulation + makeMesh's corner lookup  bowyerWatson.cpp:86-105, bestFittingPlane.cpp:67-95
+ *   slam_mesh_filter     makeMesh's edge-length filter bestFittingPlane.cpp:96-114
  *   slam_batch_*         the data-parallel candidate scan around them, batch.cpp:59-226
  *
  * Conventions
@@ -249,6 +251,52 @@ int slam_plane_moments(slam_ctx* ctx, const float* pts, int n, double* sum /* 3 
  * reference divides by zero. */
 int slam_project_to_plane(slam_ctx* ctx, const float* pts, int n, const float* centroid /* 3 */,
                           const double* normal /* 3 */, float* out_xy /* n x 2 */);
+
+/* builtInTriangulation (bowyerWatson.cpp:86-105: cv::Subdiv2D insert +
+ * getTriangleList) with makeMesh's corner lookup (bestFittingPlane.cpp:67-95)
+ * folded in: the Delaunay triangulation of n Point2f as index triples.
+ *   - Point i is a vertex iff no j < i has x_j == x_i && y_j == y_i (float ==:
+ *     makeMesh's "first k that matches"); no triangle names another point.
+ *   - The triangles are the Delaunay triangulation of the vertices, complete up
+ *     to the convex hull (collinear hull points included), decided by the exact
+ *     signs of orient2d and incircle on the f32 coordinates.
+ *   - >= 4 cocircular vertices on an empty circle: their polygon is fanned from
+ *     its lowest-indexed vertex, a function of the input alone.
+ *   - Each triangle is (i, j, k), i its smallest index, counter-clockwise in the
+ *     (x, y) given; the list is sorted lexicographically.  Two calls on the same
+ *     input return identical bytes.
+ * Fewer than 3 vertices, or all collinear: *n_tris = 0, SLAM_OK.  A coordinate
+ * that is not finite or outside [-100000, 100000) (Subdiv2D's rectangle; the
+ * reference's caller catches its exception and shows no mesh): *n_tris = 0,
+ * SLAM_E_INVALID_ARG.  cap too small: SLAM_E_CAPACITY with the needed number in
+ * *n_tris (at most 2 n - 5).  n == 0: SLAM_OK, no launch.  The work is
+ * O(n^2) exact predicates: meant for single components, not for the cloud. */
+int slam_delaunay_2d(slam_ctx* ctx, const float* xy /* n x 2 */, int n, int32_t* tris /* cap x 3 */, int cap,
+                     int* n_tris);
+/* the same on device buffers (d_xy 8-byte aligned), on `stream` (NULL = the
+ * context stream).  Unlike slam_cluster_points_dev it waits for the stream:
+ * the status depends on what the kernels found.  *d_n_tris as *n_tris above. */
+int slam_delaunay_2d_dev(slam_ctx* ctx, void* stream, const float* d_xy, int n, int32_t* d_tris, int cap,
+                         int32_t* d_n_tris);
+/* the same contract evaluated on the host with the same predicates and tie rule,
+ * one vertex after the other: no context, no device, no launch.  For inputs so
+ * small that a launch and its readbacks cost more than the triangulation; the
+ * scene drivers (slamhip.scene.make_mesh, the C++ makeMesh) send components
+ * below SLAM_DELAUNAY_HOST_BELOW points here. */
+#define SLAM_DELAUNAY_HOST_BELOW 64
+int slam_delaunay_2d_host(const float* xy /* n x 2 */, int n, int32_t* tris /* cap x 3 */, int cap, int* n_tris);
+/* counters of the context's last Delaunay call: predicates evaluated, those of
+ * them that needed the exact path, and apex searches that met an exact incircle
+ * zero and ran the tie pass
+ * (scripts/mesh_bench.py reports them) */
+int slam_delaunay_last_stats(slam_ctx* ctx, uint64_t* predicates, uint64_t* exact_predicates, uint64_t* tie_passes);
+/* makeMesh's filter (bestFittingPlane.cpp:96-114), host only: copies to `out`,
+ * in order, every triangle none of whose three edges is longer than max_size
+ * (the reference's 10000) by distance(Point3f, Point3f), geomAdditionalFunc.cpp:16-18:
+ * f32 differences, squares summed in f64, strict >.  tris index pts (0 <= index
+ * < n, else SLAM_E_INVALID_ARG); out holds n_tris triples; *n_out = the number kept. */
+int slam_mesh_filter(const float* pts /* n x 3 */, int n, const int32_t* tris /* n_tris x 3 */, int n_tris,
+                     double max_size, int32_t* out, int* n_out);
 
 /* knnMatch(query, train, k = 2): idx/dist nq x 2 (idx -1 where missing). */
 int slam_knn2(slam_ctx* ctx, const void* q, int nq, const void* t, int nt,

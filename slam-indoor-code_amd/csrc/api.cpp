@@ -418,7 +418,7 @@ void slam_destroy(slam_ctx* c)
                       &c->desc_norm, &c->desc_exp, &c->query_norm, &c->knn_part, &c->match_rec, &c->match_flag,
                       &c->match_cnt, &c->match_out, &c->frames_in, &c->qbuf, &c->tbuf, &c->misc, &c->ba_obs,
                       &c->ba_par, &c->ba_jac, &c->ba_red, &c->ba_S, &c->ba_aux, &c->sd_pyr, &c->sd_cand,
-                      &c->sd_kps, &c->sd_kpc, &c->sift_tab, &c->sift_band_buf, &c->sift_cols_buf, &c->sift_cols_park, &c->sift_colw_buf, &c->sift_split, &c->sift_split_cnt, &c->geom, &c->cluster};
+                      &c->sd_kps, &c->sd_kpc, &c->sift_tab, &c->sift_band_buf, &c->sift_cols_buf, &c->sift_cols_park, &c->sift_colw_buf, &c->sift_split, &c->sift_split_cnt, &c->geom, &c->cluster, &c->delaunay};
     for (DevBuf* b : bufs) b->release();
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->ev_up) (void)hipEventDestroy(c->ev_up);
@@ -1428,6 +1428,32 @@ int slam_order_after_stage(slam_ctx* c, void* waiter, int stage)
     if (!c->stage_recorded) return set_err(c, SLAM_E_INVALID_ARG, "no extraction queued on this context yet");
     SLAM_HIP(c, hipSetDevice(c->device));
     SLAM_HIP(c, hipStreamWaitEvent((hipStream_t)waiter, c->ev_stage[stage], 0));
+    return SLAM_OK;
+}
+
+// makeMesh:96-114 with distance(Point3f, Point3f) (geomAdditionalFunc.cpp:16-18)
+int slam_mesh_filter(const float* pts, int n, const int32_t* tris, int n_tris, double max_size, int32_t* out, int* n_out)
+{
+    if (n < 0 || n_tris < 0 || !n_out || (n_tris > 0 && (!pts || !tris || !out))) return SLAM_E_INVALID_ARG;
+    *n_out = 0;
+    int kept = 0;
+    for (int t = 0; t < n_tris; t++) {
+        const int32_t* v = tris + 3 * (size_t)t;
+        for (int q = 0; q < 3; q++)
+            if (v[q] < 0 || v[q] >= n) return SLAM_E_INVALID_ARG;
+        bool drop = false;
+        for (int q = 0; q < 3; q++) {
+            const float* a = pts + 3 * (size_t)v[q];
+            const float* b = pts + 3 * (size_t)v[(q + 1) % 3];
+            const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];      // Point3f operator-
+            const double ex = (double)dx, ey = (double)dy, ez = (double)dz;
+            if (sqrt(ex * ex + ey * ey + ez * ez) > max_size) drop = true;
+        }
+        if (drop) continue;
+        for (int q = 0; q < 3; q++) out[3 * (size_t)kept + q] = v[q];
+        kept++;
+    }
+    *n_out = kept;
     return SLAM_OK;
 }
 

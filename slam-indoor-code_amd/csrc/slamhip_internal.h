@@ -237,6 +237,10 @@ struct slam_ctx {
     slamhip::DevBuf cluster;
     unsigned long long cluster_pairs_total = 0;   // n (n - 1) / 2 of the last clustering call
     hipStream_t cluster_stats_stream = nullptr;   // ... and the stream it ran on
+    // Delaunay step (delaunay.hip): counters, duplicate marks, the triangle scratch
+    slamhip::DevBuf delaunay;
+    bool delaunay_ran = false;                    // slam_delaunay_last_stats has a call to report
+    hipStream_t delaunay_stats_stream = nullptr;  // the stream of the last call
 
     // SIFT gather table for one (angle, size) (sift_tab.hip)
     slamhip::DevBuf sift_tab;

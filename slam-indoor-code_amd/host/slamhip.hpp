@@ -222,6 +222,22 @@ void getBestFittingPlaneByPoints(const std::vector<Point3f>& points, Point3f& ce
 void projectToPlane(const std::vector<Point3f>& points, const Point3f& centroid, const Vec3d& normal,
                     std::vector<Point2f>& projected);
 
+// builtInTriangulation(points, triangulation) -- bowyerWatson.cpp:86-105, with
+// makeMesh's corner lookup (bestFittingPlane.cpp:67-95) folded in: each triangle
+// is three indices into points (the first point at those coordinates), smallest
+// first, counter-clockwise, the list sorted (include/slamhip.h, slam_delaunay_2d).
+// A coordinate that is not finite or outside [-100000, 100000), where
+// cv::Subdiv2D throws, throws Error.
+void builtInTriangulation(const std::vector<Point2f>& points, std::vector<std::array<int, 3>>& triangulation);
+
+// makeMesh(points, colors, centroid, normal) -- bestFittingPlane.cpp:41-127 without
+// the widget: project, triangulate, drop triangles with a 3-D edge longer than
+// 10000.  Returns the polygon list handed to cv::viz::WMesh: {3, i, j, k, 3, ...}
+// with indices into points.  Throws where the reference does (see above); its
+// caller catches and shows no mesh for that component.
+std::vector<int> makeMesh(const std::vector<Point3f>& points, const std::vector<Vec3b>& colors,
+                          const Point3f& centroid, const Vec3d& normal);
+
 std::array<double, 3> rodrigues(const std::array<double, 9>& R);
 std::array<double, 9> rodrigues(const std::array<double, 3>& r);
 

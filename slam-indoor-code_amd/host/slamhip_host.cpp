@@ -410,6 +410,51 @@ void projectToPlane(const std::vector<Point3f>& points, const Point3f& centroid,
           &ctx);
 }
 
+void builtInTriangulation(const std::vector<Point2f>& points, std::vector<std::array<int, 3>>& triangulation)
+{
+    static_assert(sizeof(std::array<int, 3>) == 3 * sizeof(int32_t), "triangles are packed index triples");
+    const int n = (int)points.size();
+    const int cap = std::max(2 * n - 5, 1);              // a planar triangulation of n points has at most 2n - 5
+    std::vector<std::array<int, 3>> tris((size_t)cap);
+    int nt = 0;
+    if (n < SLAM_DELAUNAY_HOST_BELOW) {                  // a launch would cost more than the work: same contract, host
+        check(slam_delaunay_2d_host(reinterpret_cast<const float*>(points.data()), n,
+                                    reinterpret_cast<int32_t*>(tris.data()), cap, &nt),
+              nullptr);
+    } else {
+        Context& ctx = Context::thread_default();
+        check(slam_delaunay_2d(ctx.get(), reinterpret_cast<const float*>(points.data()), n,
+                               reinterpret_cast<int32_t*>(tris.data()), cap, &nt),
+              &ctx);
+    }
+    tris.resize((size_t)nt);
+    triangulation.insert(triangulation.end(), tris.begin(), tris.end());
+}
+
+std::vector<int> makeMesh(const std::vector<Point3f>& points, const std::vector<Vec3b>& colors, const Point3f& centroid,
+                          const Vec3d& normal)
+{
+    if (points.size() != colors.size()) throw Error("makeMesh: points and colors differ in length");
+    std::vector<Point2f> pts;
+    projectToPlane(points, centroid, normal, pts);
+    std::vector<std::array<int, 3>> triang;
+    builtInTriangulation(pts, triang);
+    const double max_size = 10000;
+    std::vector<int32_t> kept(3 * std::max<size_t>(triang.size(), 1));
+    int nk = 0;
+    check(slam_mesh_filter(reinterpret_cast<const float*>(points.data()), (int)points.size(),
+                           reinterpret_cast<const int32_t*>(triang.data()), (int)triang.size(), max_size, kept.data(),
+                           &nk),
+          nullptr);
+    std::vector<int> poly;
+    poly.reserve(4 * (size_t)nk);
+    for (int t = 0; t < nk; t++) {
+        poly.push_back(3);
+        for (int q = 0; q < 3; q++) poly.push_back(kept[3 * (size_t)t + q]);
+    }
+    return poly;
+}
+
 bool estimateTransformation(const std::vector<Point2f>& points1, const std::vector<Point2f>& points2,
                             const std::array<double, 9>& K, std::array<double, 9>& R, std::array<double, 3>& t,
                             std::vector<uint8_t>& chiralityMask)

@@ -18,7 +18,8 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
                   getMatcherTypeIndex, knnMatch2, loss_from_config, matchFeatures, matchFramesPairFeatures,
                   rodrigues_to_matrix, rodrigues_to_vector, selectGoodFrame, synth_frames,
                   SYNTH_DRIFT, SYNTH_STEADY, synth_frames_dev,
-                  clusterizePoints, clusterLabels, getBestFittingPlaneByPoints, planeMoments, projectToPlane)
+                  clusterizePoints, clusterLabels, getBestFittingPlaneByPoints, planeMoments, projectToPlane,
+                  delaunay2d, delaunay2dHost, delaunayStats, meshFilter)
 from .config import ConfigError, ConfigService, reference_example
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -548,6 +548,65 @@ def projectToPlane(points, centroid, normal, ctx=None):
     return out[:len(p)].copy()
 
 
+MESH_MAX_SIZE = 10000.0      # makeMesh's max_size (bestFittingPlane.cpp:89)
+
+
+def delaunay2d(xy, ctx=None):
+    """builtInTriangulation (bowyerWatson.cpp:86-105) with makeMesh's corner
+    lookup (bestFittingPlane.cpp:67-95): the Delaunay triangulation of the n x 2
+    float32 points as a (T, 3) int32 array of point indices, each row starting
+    at its smallest index, counter-clockwise, rows sorted (slam_delaunay_2d has
+    the contract).  A coordinate that is not finite or outside [-100000, 100000),
+    where the reference's Subdiv2D throws, raises SlamError with
+    SLAM_E_INVALID_ARG."""
+    c = _ctx(ctx)
+    p = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    cap = max(2 * len(p) - 5, 1)
+    tris = np.zeros((cap, 3), np.int32)
+    nt = ctypes.c_int(0)
+    check(lib().slam_delaunay_2d(c, ptr(p), len(p), ptr(tris), cap, ctypes.byref(nt)), c)
+    return tris[:nt.value].copy()
+
+
+DELAUNAY_HOST_BELOW = 64     # SLAM_DELAUNAY_HOST_BELOW
+
+
+def delaunay2dHost(xy):
+    """slam_delaunay_2d_host: delaunay2d's contract evaluated on the host (the
+    same exact predicates and tie rule; no context, no device).  For inputs of
+    a few dozen points, where a launch costs more than the triangulation."""
+    p = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    cap = max(2 * len(p) - 5, 1)
+    tris = np.zeros((cap, 3), np.int32)
+    nt = ctypes.c_int(0)
+    rc = lib().slam_delaunay_2d_host(ptr(p), len(p), ptr(tris), cap, ctypes.byref(nt))
+    if rc != L.SLAM_OK:
+        raise L.SlamError(rc, "slam_delaunay_2d_host: a coordinate is not finite or outside [-100000, 100000)"
+                          if rc == L.SLAM_E_INVALID_ARG else "slam_delaunay_2d_host")
+    return tris[:nt.value].copy()
+
+
+def delaunayStats(ctx=None):
+    """slam_delaunay_last_stats: (predicates, exact-path predicates, tie passes)
+    of the context's last Delaunay call"""
+    c = _ctx(ctx)
+    v = [ctypes.c_uint64(0) for _ in range(3)]
+    check(lib().slam_delaunay_last_stats(c, *[ctypes.byref(x) for x in v]), c)
+    return tuple(int(x.value) for x in v)
+
+
+def meshFilter(points, tris, max_size=MESH_MAX_SIZE):
+    """makeMesh's filter (bestFittingPlane.cpp:96-114): the triangles (T, 3)
+    none of whose 3-D edges between points (n x 3, Point3f) is longer than
+    max_size, in order.  Host code; needs no device."""
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tris, np.int32).reshape(-1, 3)
+    out = np.zeros((max(len(t), 1), 3), np.int32)
+    kept = ctypes.c_int(0)
+    check(lib().slam_mesh_filter(ptr(p), len(p), ptr(t), len(t), float(max_size), ptr(out), ctypes.byref(kept)))
+    return out[:kept.value].copy()
+
+
 SYNTH_DRIFT, SYNTH_STEADY = 0, 1
 
 

@@ -1,0 +1,147 @@
+"""The exact predicates of the Delaunay step (slam-indoor-code_amd/csrc/exact_pred.h)
+on the CPU: tests/cpp/exact_pred_test.cpp, built with g++, prints the filter's
+and the full predicate's sign for every case of tests/golden/exact_pred_cases.txt;
+both are compared with fractions.Fraction arithmetic.  The same header is what
+the kernel compiles, so this covers the exact fallback the device runs."""
+import os
+import shutil
+import subprocess
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+import mesh_ref as M
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CASES = os.path.join(ROOT, "tests", "golden", "exact_pred_cases.txt")
+SRC = os.path.join(ROOT, "tests", "cpp", "exact_pred_test.cpp")
+F32 = np.float32
+NV = {"o": 6, "i": 8, "c": 6}
+
+
+def nudge(v, rng):
+    """every value moved by one f32 ulp, up or down, or left alone"""
+    v = np.asarray(v, F32)
+    k = rng.integers(-1, 2, v.shape)
+    return np.where(k > 0, np.nextafter(v, F32(np.inf)), np.where(k < 0, np.nextafter(v, F32(-np.inf)), v)).astype(F32)
+
+
+def generate_cases():
+    """the committed list, rebuilt (test_committed_cases_are_the_generated_ones)"""
+    rng = np.random.default_rng(20231)
+    out = []
+
+    def add(kind, vals):
+        vals = np.asarray(vals, F32).reshape(-1)
+        assert len(vals) == NV[kind] and np.isfinite(vals).all() and (np.abs(vals) <= 100000).all()
+        out.append(kind + " " + " ".join(f"{int(b):08x}" for b in vals.view(np.uint32)))
+
+    # random points at several scales
+    for kind in "oic":
+        for t in range(120):
+            scale = 10.0 ** rng.uniform(-6, 4.9)
+            add(kind, np.clip(rng.normal(0, scale, NV[kind]), -99999, 99999))
+    # exactly collinear integer triples, then the same with single-ulp nudges
+    for t in range(120):
+        a = rng.integers(-2000, 2000, 2)
+        d = rng.integers(-30, 31, 2)
+        s, u = rng.integers(-40, 41, 2)
+        tri = np.array([a, a + s * d, a + u * d], F32) * F32(2.0 ** int(rng.integers(-20, 4)))
+        add("o", tri)
+        add("o", nudge(tri, rng))
+    # exactly cocircular integer quadruples (radius 5, 25, 65, 85 circles), shifted, scaled, nudged
+    circles = {}
+    for r2 in (25, 625, 4225, 7225):
+        r = int(r2 ** 0.5)
+        circles[r2] = [(x, y) for x in range(-r, r + 1) for y in range(-r, r + 1) if x * x + y * y == r2]
+    for t in range(150):
+        pts = circles[(25, 625, 4225, 7225)[t % 4]]
+        q = np.array([pts[k] for k in rng.choice(len(pts), 4, replace=False)], np.int64) + rng.integers(-500, 500, 2)
+        q = q.astype(F32) * F32(2.0 ** int(rng.integers(-12, 4)))
+        if M.orient2d(*[(Fraction(float(x)), Fraction(float(y))) for x, y in q[:3]]) == 0:
+            continue
+        add("i", q)
+        add("i", nudge(q, rng))
+    # equal distances (Pythagorean pairs about a common point), then nudged
+    legs = ([(3, 4), (5, 0), (-4, 3), (0, -5), (4, -3), (-3, -4)],
+            [(33, 56), (63, 16), (-16, 63), (65, 0), (25, 60), (39, 52)])
+    for t in range(100):
+        a = rng.integers(-3000, 3000, 2)
+        group = legs[t % 2]
+        k = rng.choice(len(group), 2, replace=False)
+        p, q = np.array(group[k[0]]), np.array(group[k[1]])
+        v = np.array([a, a + p, a + q], F32) * F32(2.0 ** int(rng.integers(-16, 3)))
+        add("c", v)
+        add("c", nudge(v, rng))
+    # mixed magnitudes: 1e-30 next to 9e4, and the smallest subnormal next to the range limit
+    pool = np.array([1e-30, -1e-30, 9e4, -9e4, 1.0, 3e-39, 1.401298464324817e-45, -1.401298464324817e-45,
+                     99999.9921875, -100000.0, 0.5, 12345.678, 7e-20], F32)
+    for kind in "oic":
+        for t in range(100):
+            add(kind, pool[rng.integers(0, len(pool), NV[kind])])
+    # signed zeros, repeated points and all-equal inputs
+    z = np.array([0.0, -0.0, 1.0, -1.0, 2.0], F32)
+    for kind in "oic":
+        for t in range(60):
+            add(kind, z[rng.integers(0, len(z), NV[kind])])
+    return "\n".join(out) + "\n"
+
+
+def read_cases():
+    with open(CASES) as f:
+        rows = [line.split() for line in f if line.strip()]
+    cases = []
+    for r in rows:
+        vals = np.array([int(h, 16) for h in r[1:]], np.uint32).view(F32)
+        assert len(vals) == NV[r[0]]
+        cases.append((r[0], [Fraction(float(v)) for v in vals]))
+    return cases
+
+
+def exact_sign(kind, v):
+    if kind == "o":
+        return M.orient2d(v[0:2], v[2:4], v[4:6])
+    if kind == "i":
+        return M.incircle(v[0:2], v[2:4], v[4:6], v[6:8])
+    return M.closer(v[0:2], v[2:4], v[4:6])
+
+
+def test_committed_cases_are_the_generated_ones():
+    with open(CASES) as f:
+        assert f.read() == generate_cases()
+
+
+def run_driver(tmp_path, extra, name):
+    exe = str(tmp_path / name)
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", *extra, "-o", exe, SRC], check=True)
+    r = subprocess.run([exe, CASES], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    return [tuple(int(t) for t in line.split()) for line in r.stdout.splitlines()]
+
+
+@pytest.fixture(scope="module")
+def expected():
+    cases = read_cases()
+    return cases, [exact_sign(k, v) for k, v in cases]
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+@pytest.mark.parametrize("flags", [(), ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g")],
+                         ids=["plain", "asan-ubsan"])
+def test_predicates_against_fractions(tmp_path, expected, flags):
+    cases, want = expected
+    got = run_driver(tmp_path, flags, "exact_pred_test")
+    assert len(got) == len(cases)
+    undecided = {"o": 0, "i": 0, "c": 0}
+    zeros = {"o": 0, "i": 0, "c": 0}
+    for n, ((kind, _), w, (fs, s)) in enumerate(zip(cases, want, got)):
+        assert s == w, (n, kind, s, w)
+        assert fs == w or fs == 2, (n, kind, "the filter alone returned a wrong sign", fs, w)   # never a wrong sign
+        undecided[kind] += fs == 2
+        zeros[kind] += w == 0
+    # the list reaches the exact path, exact zeros and both signs of every predicate
+    for kind in "oic":
+        assert undecided[kind] >= 50 and zeros[kind] >= 30, (kind, undecided, zeros)
+        signs = {w for (k, _), w in zip(cases, want) if k == kind}
+        assert signs == {-1, 0, 1}

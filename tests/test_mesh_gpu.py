@@ -1,0 +1,251 @@
+"""GPU tests of the Delaunay step (csrc/delaunay.hip) and the mesh it feeds:
+every small result must equal tests/mesh_ref.py's exact reference byte for
+byte; larger ones pass its O(T) verifier (and equal scipy's set where scipy
+imports)."""
+import ctypes
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import mesh_ref as M
+import scene_ref as R
+import slamhip
+from slamhip import _lib as L
+from slamhip import api, scene
+
+pytestmark = pytest.mark.gpu
+
+F32 = np.float32
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def raw(ctx, xy, cap=None):
+    """slam_delaunay_2d as called through ctypes: (status, n_tris, tris[:cap])"""
+    xy = np.ascontiguousarray(xy, F32).reshape(-1, 2)
+    cap = max(2 * len(xy), 1) if cap is None else cap
+    tris = np.full((max(cap, 1), 3), -9, np.int32)
+    nt = ctypes.c_int(-1)
+    rc = slamhip.lib().slam_delaunay_2d(ctx.handle, L.ptr(xy) if len(xy) else None, len(xy), L.ptr(tris), cap,
+                                        ctypes.byref(nt))
+    return rc, nt.value, tris
+
+
+def same_bytes(got, ref):
+    assert got.dtype == np.int32 and got.shape == ref.shape, (got.shape, ref.shape)
+    assert got.tobytes() == ref.tobytes()
+
+
+@pytest.mark.parametrize("n", [0, 1, 2, 3, 4, 5, 63, 64, 65, 127, 128, 129, 257])
+def test_uniform_points_equal_the_reference(gpu_ctx, n):
+    xy = M.uniform(n)
+    same_bytes(api.delaunay2d(xy, ctx=gpu_ctx), M.delaunay_ref(xy))
+
+
+DEGENERATE = [M.grid, M.circle12, M.circle12_centre, M.circle12_around]
+
+
+@pytest.mark.parametrize("make", DEGENERATE, ids=lambda f: f.__name__)
+def test_cocircular_sets_take_the_tie_rule(gpu_ctx, make):
+    xy = make()
+    ref = M.delaunay_ref(xy)
+    got = api.delaunay2d(xy, ctx=gpu_ctx)
+    pred, exact, ties = api.delaunayStats(ctx=gpu_ctx)
+    same_bytes(got, ref)
+    M.check_delaunay(xy, got)
+    assert ties > 0 and 0 < exact <= pred
+    same_bytes(api.delaunay2d(xy, ctx=gpu_ctx), got)            # a second call: identical bytes
+
+
+def test_nearly_cocircular_points_need_the_exact_path(gpu_ctx):
+    xy = M.circle_nudged()
+    assert len(xy) == 100
+    got = api.delaunay2d(xy, ctx=gpu_ctx)
+    pred, exact, ties = api.delaunayStats(ctx=gpu_ctx)
+    same_bytes(got, M.delaunay_ref(xy))
+    assert exact > 0 and pred > 100 * 99
+
+
+def test_duplicates_and_signed_zero(gpu_ctx):
+    xy = M.duplicates()
+    assert len(xy) == 52 and len(M.vertices(xy)) <= 41
+    got = api.delaunay2d(xy, ctx=gpu_ctx)
+    same_bytes(got, M.delaunay_ref(xy))
+    assert set(got.ravel().tolist()) == set(M.vertices(xy))     # first copies only, every one of them
+
+
+def test_collinear_points(gpu_ctx):
+    assert api.delaunay2d(M.collinear(), ctx=gpu_ctx).shape == (0, 3)
+    xy = M.collinear_plus_one()
+    same_bytes(api.delaunay2d(xy, ctx=gpu_ctx), M.delaunay_ref(xy))
+    same = np.full((70, 2), 2.5, F32)                            # one vertex, 69 copies
+    assert api.delaunay2d(same, ctx=gpu_ctx).shape == (0, 3)
+
+
+def test_3000_points_many_workgroups(gpu_ctx):
+    xy = M.uniform(3000)
+    got = api.delaunay2d(xy, ctx=gpu_ctx)
+    M.check_delaunay(xy, got)
+    pred, exact, ties = api.delaunayStats(ctx=gpu_ctx)
+    assert pred > 3000 * 2999 and exact < pred // 1000           # uniform points: the filter decides
+    try:
+        from scipy.spatial import Delaunay
+    except ImportError:
+        return
+    p = xy.astype(np.float64)
+    s = Delaunay(p).simplices
+    a, b, c = p[s[:, 0]], p[s[:, 1]], p[s[:, 2]]
+    cw = (b[:, 0] - a[:, 0]) * (c[:, 1] - a[:, 1]) - (b[:, 1] - a[:, 1]) * (c[:, 0] - a[:, 0]) < 0
+    s[cw] = s[cw][:, [0, 2, 1]]
+    same_bytes(got, M.canonical(s))
+
+
+def test_rejected_inputs_then_a_valid_call(gpu_ctx):
+    good = M.uniform(65)
+    ref = M.delaunay_ref(good)
+    for bad in (100000.0, np.inf, -np.inf, np.nan, float(np.nextafter(F32(-100000), F32(-np.inf)))):
+        for col in (0, 1):
+            xy = good.copy()
+            xy[37, col] = bad
+            rc, nt, _ = raw(gpu_ctx, xy)
+            assert rc == L.SLAM_E_INVALID_ARG and nt == 0, (bad, col, rc, nt)
+            with pytest.raises(slamhip.SlamError):
+                api.delaunay2d(xy, ctx=gpu_ctx)
+            seg = scene.Segment(np.arange(65, dtype=np.int32), np.zeros((65, 3), F32), np.zeros((65, 3), np.uint8), xy)
+            assert scene.make_mesh(seg, ctx=gpu_ctx) is None
+        same_bytes(api.delaunay2d(good, ctx=gpu_ctx), ref)       # the context is fine afterwards
+    # the rectangle's lower edge belongs to it
+    xy = good.copy()
+    xy[37] = (-100000.0, float(np.nextafter(F32(100000), F32(0))))
+    got = api.delaunay2d(xy, ctx=gpu_ctx)
+    same_bytes(got, M.delaunay_ref(xy))
+
+
+def test_capacity_and_argument_checks(gpu_ctx):
+    xy = M.uniform(64)
+    ref = M.delaunay_ref(xy)
+    rc, nt, tris = raw(gpu_ctx, xy, cap=len(ref))
+    assert rc == L.SLAM_OK and nt == len(ref)
+    same_bytes(tris[:nt].copy(), ref)
+    rc, nt, _ = raw(gpu_ctx, xy, cap=len(ref) - 1)
+    assert rc == L.SLAM_E_CAPACITY and nt == len(ref)
+    rc, nt, _ = raw(gpu_ctx, xy, cap=0)
+    assert rc == L.SLAM_E_CAPACITY and nt == len(ref)
+    rc, nt, _ = raw(gpu_ctx, np.zeros((0, 2), F32))
+    assert rc == L.SLAM_OK and nt == 0
+    lib = slamhip.lib()
+    n_out = ctypes.c_int(3)
+    assert lib.slam_delaunay_2d(gpu_ctx.handle, None, 5, None, 0, ctypes.byref(n_out)) == L.SLAM_E_INVALID_ARG
+    assert lib.slam_delaunay_2d(gpu_ctx.handle, L.ptr(xy), -1, None, 0, ctypes.byref(n_out)) == L.SLAM_E_INVALID_ARG
+    assert lib.slam_delaunay_2d(gpu_ctx.handle, L.ptr(xy), 64, None, 0, None) == L.SLAM_E_INVALID_ARG
+
+
+def test_device_pointer_entry(gpu_ctx):
+    import torch
+    xy = M.uniform(129)
+    ref = M.delaunay_ref(xy)
+    dev = torch.device("cuda", gpu_ctx.device)
+    d_xy = torch.from_numpy(xy).to(dev)
+    d_tris = torch.full((2 * len(xy), 3), -7, dtype=torch.int32, device=dev)
+    d_n = torch.full((1,), -7, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)
+    lib = slamhip.lib()
+
+    def call(cap):
+        return lib.slam_delaunay_2d_dev(gpu_ctx.handle, None, ctypes.c_void_p(d_xy.data_ptr()), len(xy),
+                                        ctypes.c_void_p(d_tris.data_ptr()), cap, ctypes.c_void_p(d_n.data_ptr()))
+
+    assert call(2 * len(xy)) == L.SLAM_OK
+    L.check(lib.slam_synchronize(gpu_ctx.handle), gpu_ctx.handle)
+    assert int(d_n.cpu()[0]) == len(ref)
+    got = d_tris.cpu().numpy()
+    same_bytes(got[:len(ref)].copy(), ref)
+    assert (got[len(ref):] == -7).all()                          # nothing past the list is written
+    assert call(len(ref) - 1) == L.SLAM_E_CAPACITY
+    L.check(lib.slam_synchronize(gpu_ctx.handle), gpu_ctx.handle)
+    assert int(d_n.cpu()[0]) == len(ref)
+    d_xy[5, 1] = float("nan")
+    torch.cuda.synchronize(dev)
+    assert call(2 * len(xy)) == L.SLAM_E_INVALID_ARG
+    L.check(lib.slam_synchronize(gpu_ctx.handle), gpu_ctx.handle)
+    assert int(d_n.cpu()[0]) == 0
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_cpp_host_layer_make_mesh(gpu_ctx, tmp_path):
+    """slamhip::makeMesh (host/slamhip.hpp) returns the reference's polygon list
+    {3, i, j, k, ...}: the same triangles as scene.make_mesh, below and above
+    the host / device split, and it throws where Subdiv2D would"""
+    libdir = os.path.join(ROOT, "slam-indoor-code_amd", "slamhip")
+    exe = str(tmp_path / "mesh_host_test")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "cpp", "mesh_host_test.cpp"),
+                    "-L" + libdir, "-lslamhip_host", "-lslamhip", "-Wl,-rpath," + libdir], check=True)
+    rng = np.random.default_rng(23)
+    centroid = np.array([0.25, -1.0, 2.0], F32)
+    normal = np.array([0.1, 0.98, -0.15])
+    normal /= np.linalg.norm(normal)
+    for n, spoil in ((40, None), (150, None), (150, 1e9)):
+        pts = (rng.normal(0, 2, (n, 3)) * [1, 0.05, 1] + centroid).astype(F32)
+        if spoil:
+            pts[11, 0] = spoil                                   # projects outside Subdiv2D's rectangle
+        path = tmp_path / f"in_{n}.txt"
+        rows = [" ".join(repr(float(v)) for v in centroid), " ".join(repr(float(v)) for v in normal), str(n)]
+        rows += [" ".join(repr(float(v)) for v in p) for p in pts]
+        path.write_text("\n".join(rows) + "\n")
+        r = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stdout + r.stderr
+        xy = api.projectToPlane(pts, centroid, normal, ctx=gpu_ctx)
+        seg = scene.Segment(np.arange(n, dtype=np.int32), pts, np.zeros((n, 3), np.uint8), xy)
+        m = scene.make_mesh(seg, ctx=gpu_ctx)
+        if spoil:
+            assert m is None and r.stdout.strip() == "throw"
+            continue
+        M.check_delaunay(xy, m.triangles)
+        poly = np.array(r.stdout.split()[1:], np.int32).reshape(-1, 4)
+        assert r.stdout.startswith("poly") and (poly[:, 0] == 3).all()
+        assert np.array_equal(poly[:, 1:], m.triangles) and len(poly) > n
+
+
+def test_scene_main_writes_the_mesh(gpu_ctx, tmp_path):
+    """clustered cloud -> result files -> scene.main -> mesh.ply"""
+    import json
+    from slamhip import cycle
+    pts, cols = R.clustered_cloud(4000)
+    gd = cycle.GlobalData()
+    gd.push_points(pts.astype(np.float64), cols)
+    logs = cycle.Logs(str(tmp_path))
+    logs.pose(np.eye(3), np.zeros((3, 1)))
+    logs.close(gd)
+    cfg = slamhip.reference_example()
+    min_points = 6
+    cfg.update(TriangleMaxDistance=0.25, TriangleEuclidDistanceWeight=1.0, TriangleColorDistance=0.02,
+               TriangleMinimumPoints=min_points, onlyViz=True, outputDataDir=str(tmp_path))
+    cfg_path = tmp_path / "config.json"
+    cfg_path.write_text(json.dumps(cfg))
+    segs = scene.main(str(cfg_path))
+    assert len(segs) >= 30
+    clusters = (tmp_path / "clusters.txt").read_text().splitlines()
+    assert [ln.split() for ln in clusters] == [[str(int(i)) for i in s.indices] for s in segs]   # unchanged output
+    v, c, f = M.parse_ply(str(tmp_path / "mesh.ply"))
+    loaded = scene.load_global_data(str(tmp_path))
+    assert np.array_equal(v.astype(F32), loaded.spatialPoints.astype(F32)) and len(v) == 4000
+    assert np.array_equal(c, np.asarray(loaded.spatialPointsColors, np.uint8).reshape(-1, 3)[:, ::-1])
+    assert (f[:, 0] == 3).all() and f[:, 1:].min() >= 0 and f[:, 1:].max() < 4000
+    meshes = scene.mesh(segs, ctx=gpu_ctx)
+    want = []
+    for s, m in zip(segs, meshes):
+        assert len(s.indices) >= min_points
+        if not M.in_range(s.xy):
+            assert m is None
+            continue
+        M.check_delaunay(s.xy, m.triangles)                      # nothing here is near the 10000 filter
+        assert np.array_equal(m.faces, s.indices[m.triangles])
+        want.append(m.faces)
+    assert len(want) >= 30
+    assert np.array_equal(f[:, 1:], np.concatenate(want))
+    # points of components below TriangleMinimumPoints are in no face
+    kept = np.concatenate([s.indices for s in segs])
+    small = np.setdiff1d(np.arange(4000), kept)
+    assert len(small) > 0 and not np.isin(f[:, 1:], small).any()
