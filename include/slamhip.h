@@ -290,6 +290,16 @@ int slam_delaunay_2d_host(const float* xy /* n x 2 */, int n, int32_t* tris /* c
  * zero and ran the tie pass
  * (scripts/mesh_bench.py reports them) */
 int slam_delaunay_last_stats(slam_ctx* ctx, uint64_t* predicates, uint64_t* exact_predicates, uint64_t* tie_passes);
+/* the kernel's own predicates on the device, one thread per case, so that their
+ * signs can be tested there (host pointers).  kind[i] = 'o': orient2d(a, b, c),
+ * vals[8 i ..] = ax ay bx by cx cy; 'i': incircle(a, b, c, d), ax .. dy; 'c':
+ * closer(a, p, q), ax ay px py qx qy; any other kind: SLAM_E_INVALID_ARG.
+ * filter_sign[i] = what the f64 filter alone answers (-1, 0, 1, or 2 = undecided),
+ * sign[i] = the exact sign as the star kernel gets it (filter, then the exact
+ * path).  Coordinates as for slam_delaunay_2d: finite, magnitude <= 100000.
+ * n == 0: SLAM_OK. */
+int slam_delaunay_predicates(slam_ctx* ctx, const uint8_t* kind /* n */, const float* vals /* n x 8 */, int n,
+                             int8_t* filter_sign /* n */, int8_t* sign /* n */);
 /* makeMesh's filter (bestFittingPlane.cpp:96-114), host only: copies to `out`,
  * in order, every triangle none of whose three edges is longer than max_size
  * (the reference's 10000) by distance(Point3f, Point3f), geomAdditionalFunc.cpp:16-18:

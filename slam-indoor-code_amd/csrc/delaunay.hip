@@ -312,6 +312,32 @@ __global__ __launch_bounds__(256) void tri_bitonic_tile(Tri* t, int padded, int 
     t[i] = tile[threadIdx.x];
 }
 
+// one predicate per thread through the wrappers apex uses (slam_delaunay_predicates):
+// kind 'o' orient(v0..5), 'i' incircle(v0..7), 'c' closer(v0..5)
+__global__ __launch_bounds__(64) void predicate_cases(const uint8_t* __restrict__ kind, const float* __restrict__ vals,
+                                                      int n, int8_t* __restrict__ filter_sign, int8_t* __restrict__ sign)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const float* v = vals + (size_t)i * 8;
+    const float2 a = make_float2(v[0], v[1]), b = make_float2(v[2], v[3]), p = make_float2(v[4], v[5]);
+    Ctr k;
+    int fs, s;
+    if (kind[i] == 'o') {
+        fs = exact_pred::orient2d_filter(a.x, a.y, b.x, b.y, p.x, p.y);
+        s = orient(a, b, p, k);
+    } else if (kind[i] == 'i') {
+        const float2 d = make_float2(v[6], v[7]);
+        fs = exact_pred::incircle_filter(a.x, a.y, b.x, b.y, p.x, p.y, d.x, d.y);
+        s = incircle(a, b, p, d, k);
+    } else {
+        fs = exact_pred::closer_filter(a.x, a.y, b.x, b.y, p.x, p.y);
+        s = closer(a, b, p, k);
+    }
+    filter_sign[i] = (int8_t)fs;
+    sign[i] = (int8_t)s;
+}
+
 int next_pow2(long long v)
 {
     long long p = 1;
@@ -435,6 +461,32 @@ int slam_delaunay_last_stats(slam_ctx* c, uint64_t* predicates, uint64_t* exact_
     *predicates = h.pred;
     *exact_predicates = h.exact;
     *tie_passes = h.ties;
+    return SLAM_OK;
+}
+
+int slam_delaunay_predicates(slam_ctx* c, const uint8_t* kind, const float* vals, int n, int8_t* filter_sign,
+                             int8_t* sign)
+{
+    if (!c || n < 0 || !kind || !vals || !filter_sign || !sign) return SLAM_E_INVALID_ARG;
+    for (int i = 0; i < n; i++)
+        if (kind[i] != 'o' && kind[i] != 'i' && kind[i] != 'c') return SLAM_E_INVALID_ARG;
+    if (n == 0) return SLAM_OK;
+    SLAM_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t nb = ((size_t)n + 255) & ~(size_t)255, vb = (size_t)n * 8 * sizeof(float);
+    SLAM_HIP(c, c->geom.ensure(vb + 3 * nb));
+    char* base = c->geom.as<char>();
+    float* d_vals = reinterpret_cast<float*>(base);
+    uint8_t* d_kind = reinterpret_cast<uint8_t*>(base + vb);
+    int8_t* d_fs = reinterpret_cast<int8_t*>(base + vb + nb);
+    int8_t* d_s = reinterpret_cast<int8_t*>(base + vb + 2 * nb);
+    SLAM_HIP(c, hipMemcpyAsync(d_vals, vals, vb, hipMemcpyHostToDevice, s));
+    SLAM_HIP(c, hipMemcpyAsync(d_kind, kind, (size_t)n, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(predicate_cases, dim3((n + 63) / 64), dim3(64), 0, s, d_kind, d_vals, n, d_fs, d_s);
+    SLAM_HIP(c, hipGetLastError());
+    SLAM_HIP(c, hipMemcpyAsync(filter_sign, d_fs, (size_t)n, hipMemcpyDeviceToHost, s));
+    SLAM_HIP(c, hipMemcpyAsync(sign, d_s, (size_t)n, hipMemcpyDeviceToHost, s));
+    SLAM_HIP(c, hipStreamSynchronize(s));
     return SLAM_OK;
 }
 

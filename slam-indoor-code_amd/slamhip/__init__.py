@@ -19,7 +19,7 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
                   rodrigues_to_matrix, rodrigues_to_vector, selectGoodFrame, synth_frames,
                   SYNTH_DRIFT, SYNTH_STEADY, synth_frames_dev,
                   clusterizePoints, clusterLabels, getBestFittingPlaneByPoints, planeMoments, projectToPlane,
-                  delaunay2d, delaunay2dHost, delaunayStats, meshFilter)
+                  delaunay2d, delaunay2dHost, delaunayStats, delaunayPredicates, meshFilter)
 from .config import ConfigError, ConfigService, reference_example
 
 __all__ = [n for n in dir() if not n.startswith("_")]

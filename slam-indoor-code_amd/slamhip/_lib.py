@@ -115,6 +115,7 @@ SIGNATURES = {
     "slam_delaunay_2d": (_I, [_P, _P, _I, _P, _I, _P]),
     "slam_delaunay_2d_dev": (_I, [_P, _P, _P, _I, _P, _I, _P]),
     "slam_delaunay_last_stats": (_I, [_P, _P, _P, _P]),
+    "slam_delaunay_predicates": (_I, [_P, _P, _P, _I, _P, _P]),
     "slam_delaunay_2d_host": (_I, [_P, _I, _P, _I, _P]),
     "slam_mesh_filter": (_I, [_P, _I, _P, _I, _D, _P, _P]),
 }

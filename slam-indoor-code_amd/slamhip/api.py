@@ -595,6 +595,25 @@ def delaunayStats(ctx=None):
     return tuple(int(x.value) for x in v)
 
 
+def delaunayPredicates(kinds, vals, ctx=None):
+    """slam_delaunay_predicates: the star kernel's orient ('o'), incircle ('i')
+    and closer ('c') evaluated on the device, one case per row of vals (n x 8
+    float32; 'o' and 'c' read the first six).  kinds is a str or bytes of n
+    letters.  Returns (filter_sign, sign), int8[n]: the f64 filter's answer
+    alone (2 = undecided) and the exact sign."""
+    c = _ctx(ctx)
+    k = np.frombuffer(kinds.encode() if isinstance(kinds, str) else bytes(kinds), np.uint8).copy()
+    v = np.ascontiguousarray(vals, np.float32).reshape(-1, 8)
+    if len(k) != len(v):
+        raise ValueError("delaunayPredicates: one kind per row of vals")
+    n = len(k)
+    fs, s = np.zeros(max(n, 1), np.int8), np.zeros(max(n, 1), np.int8)
+    if n == 0:
+        k, v = np.zeros(1, np.uint8), np.zeros((1, 8), np.float32)
+    check(lib().slam_delaunay_predicates(c, ptr(k), ptr(v), n, ptr(fs), ptr(s)), c)
+    return fs[:n].copy(), s[:n].copy()
+
+
 def meshFilter(points, tris, max_size=MESH_MAX_SIZE):
     """makeMesh's filter (bestFittingPlane.cpp:96-114): the triangles (T, 3)
     none of whose 3-D edges between points (n x 3, Point3f) is longer than

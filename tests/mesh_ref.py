@@ -12,6 +12,7 @@ delaunay_ref and check_delaunay scale all coordinates of one input by their
 common denominator (found with Fraction) so that the predicates run on Python
 integers: the same exact values, about ten times faster than Fraction objects.
 """
+import math
 from fractions import Fraction
 
 import numpy as np
@@ -294,3 +295,129 @@ def collinear(n=10):
 
 def collinear_plus_one():
     return np.concatenate([collinear(), np.array([[3.5, -4.0]], np.float32)])
+
+
+# ---- adversarial sets: more tie members than lanes, tile-crossing duplicates, the ends of
+# ---- the coordinate range, triangle counts at the sort's powers of two
+
+def _shuffled(pts, seed):
+    pts = np.ascontiguousarray(pts, np.float32)
+    return pts[np.random.default_rng(seed).permutation(len(pts))]
+
+
+def lattice_circle(R=1105, seed=7):
+    """every integer point on the circle of radius R about the origin, shuffled.
+    1105 = 5 * 13 * 17: 108 points (32045 = 5 * 13 * 17 * 29: 324), exact in f32:
+    more cocircular vertices than a wave has lanes, one fan of len - 2 triangles"""
+    c = set()
+    for x in range(-R, R + 1):
+        y = math.isqrt(R * R - x * x)
+        if x * x + y * y == R * R:
+            c.update([(x, y), (x, -y)])
+    c = sorted(c)
+    assert R < 2 ** 24
+    return _shuffled(c, seed)
+
+
+def lattice_circle_centre(R=1105, seed=7):
+    """the origin inserted at index 50: every circle point has an edge to it"""
+    c = lattice_circle(R, seed)
+    return np.concatenate([c[:50], np.zeros((1, 2), np.float32), c[50:]])
+
+
+def lattice_circle_around(R=1105, seed=7):
+    """the circle around 40 inner points, uniform in +-500"""
+    inner = np.random.default_rng(seed + 100).uniform(-500, 500, (40, 2)).astype(np.float32)
+    return _shuffled(np.concatenate([lattice_circle(R, seed), inner]), seed + 200)
+
+
+def grid272():
+    """17 x 16: four-point ties everywhere, across the 256-point tile of the pre-pass"""
+    return grid(17, 16)
+
+
+def near_9e4():
+    """300 points on the 2^-7 lattice next to 90000 (formed in f32): duplicates,
+    collinear runs, cocircular quadruples, lifted terms near 1e20"""
+    xy = uniform(300) * np.float32(0.002) + np.float32(90000)
+    assert xy.dtype == np.float32
+    return xy
+
+
+def full_range():
+    """200 points over nearly all of [-100000, 100000)"""
+    xy = uniform(200, seed=5) * np.float32(1999.9)
+    assert xy.dtype == np.float32
+    return xy
+
+
+def mixed_magnitudes(seed=29):
+    """130 points: 60 of order 1e-30, 30 small integer multiples of the smallest
+    f32 subnormal, 40 uniform in +-9e4, shuffled"""
+    rng = np.random.default_rng(seed)
+    tiny = (rng.uniform(-5, 5, (60, 2)) * 1e-30).astype(np.float32)
+    sub = (rng.integers(-20, 20, (30, 2)).astype(np.int64).astype(np.float64) * 2.0 ** -149).astype(np.float32)
+    assert (sub.astype(np.float64) * 2.0 ** 149 == np.round(sub.astype(np.float64) * 2.0 ** 149)).all()
+    big = rng.uniform(-9e4, 9e4, (40, 2)).astype(np.float32)
+    return _shuffled(np.concatenate([tiny, sub, big]), seed + 1)
+
+
+def dups650(seed=31):
+    """400 points and 250 copies drawn from them, shuffled: three pre-pass tiles"""
+    p = uniform(400)
+    rng = np.random.default_rng(seed)
+    return _shuffled(np.concatenate([p, p[rng.integers(0, 400, 250)]]), seed + 1)
+
+
+def dups_tile_edges():
+    """640 points with four copies, each with its first occurrence in an earlier
+    256-point tile of the pre-pass: the last point of the tile before, the first
+    point of the first tile, a third copy two tiles back, and mid-tile to the end"""
+    xy = uniform(640).copy()
+    xy[256] = xy[255]
+    xy[511] = xy[0]
+    xy[512] = xy[256]
+    xy[639] = xy[300]
+    return xy
+
+
+def hull3(n):
+    """n - 3 points inside a triangle and its corners: 2 n - 5 triangles (Euler)"""
+    return np.concatenate([uniform(n - 3), np.array([[0, 300], [-300, -100], [300, -100]], np.float32)])
+
+
+def hull4(n):
+    """n - 4 points inside a square and its corners: 2 n - 6 triangles"""
+    return np.concatenate([uniform(n - 4), np.array([[-300, -300], [300, -300], [300, 300], [-300, 300]], np.float32)])
+
+
+# (name, maker, what the device counters must show: "ties" = ties > 0 and exact > 0, "exact", None)
+ADVERSARIAL = [
+    ("lattice_circle_s7", lambda: lattice_circle(seed=7), "ties"),
+    ("lattice_circle_s8", lambda: lattice_circle(seed=8), "ties"),
+    ("lattice_circle_centre_s7", lambda: lattice_circle_centre(seed=7), "ties"),
+    ("lattice_circle_centre_s8", lambda: lattice_circle_centre(seed=8), "ties"),
+    ("lattice_circle_around_s7", lambda: lattice_circle_around(seed=7), "ties"),
+    ("lattice_circle_around_s8", lambda: lattice_circle_around(seed=8), "ties"),
+    ("lattice_circle_32045", lambda: lattice_circle(32045, seed=9), "ties"),
+    ("grid272", grid272, "ties"),
+    ("near_9e4", near_9e4, "ties"),
+    ("full_range", full_range, None),
+    ("mixed_magnitudes", mixed_magnitudes, "exact"),
+    ("dups650", dups650, None),
+    ("dups_tile_edges", dups_tile_edges, None),
+]
+HULL_COUNTS = [(hull3, 130, 255), (hull3, 131, 257), (hull3, 259, 513), (hull4, 131, 256), (hull4, 259, 512)]
+
+_REF_CACHE = {}
+
+
+def cached_ref(name, make):
+    """(xy, delaunay_ref(xy)) of a named fixture, computed once per process; treat both as read-only"""
+    if name not in _REF_CACHE:
+        xy = make()
+        ref = delaunay_ref(xy)
+        xy.setflags(write=False)
+        ref.setflags(write=False)
+        _REF_CACHE[name] = (xy, ref)
+    return _REF_CACHE[name]

@@ -1,8 +1,8 @@
 """The exact predicates of the Delaunay step (slam-indoor-code_amd/csrc/exact_pred.h)
 on the CPU: tests/cpp/exact_pred_test.cpp, built with g++, prints the filter's
 and the full predicate's sign for every case of tests/golden/exact_pred_cases.txt;
-both are compared with fractions.Fraction arithmetic.  The same header is what
-the kernel compiles, so this covers the exact fallback the device runs."""
+both are compared with fractions.Fraction arithmetic.  The device build of the
+same header is tested in tests/test_exact_pred_gpu.py."""
 import os
 import shutil
 import subprocess
@@ -27,9 +27,10 @@ def nudge(v, rng):
     return np.where(k > 0, np.nextafter(v, F32(np.inf)), np.where(k < 0, np.nextafter(v, F32(-np.inf)), v)).astype(F32)
 
 
-def generate_cases():
-    """the committed list, rebuilt (test_committed_cases_are_the_generated_ones)"""
-    rng = np.random.default_rng(20231)
+def generate_cases(seed=20231):
+    """the committed list, rebuilt (test_committed_cases_are_the_generated_ones);
+    another seed gives another list of the same make (tests/test_exact_pred_gpu.py)"""
+    rng = np.random.default_rng(seed)
     out = []
 
     def add(kind, vals):
@@ -88,15 +89,56 @@ def generate_cases():
     return "\n".join(out) + "\n"
 
 
-def read_cases():
-    with open(CASES) as f:
-        rows = [line.split() for line in f if line.strip()]
+def generate_lifted_cases(seed=20232):
+    """incircle rows whose sign hangs on the low part of two_prod (the committed
+    list decides every row without it); products of four coordinates near 6.6e19,
+    far above 2^53, on the 2^-7 lattice next to +-90000 where f32 has no bit to spare.
+      even rows  integer cocircular quadruples moved onto that lattice: exact zeros
+      odd rows   (A, 0), (0, B), (A, B) on a circle through the origin, and d a
+                 point of order 1e-30 or a subnormal next to the origin: the
+                 differences round d away, the filter sees a zero, and the exact
+                 determinant is about 1e-15 under terms of 6.6e19
+    Not part of the committed file."""
+    rng = np.random.default_rng(seed)
+    out = []
+
+    def add(q):
+        q = np.asarray(q, F32)
+        assert q.shape == (4, 2) and (np.abs(q) < 100000).all()
+        out.append("i " + " ".join(f"{int(b):08x}" for b in q.reshape(-1).view(np.uint32)))
+
+    circles = {}
+    for r2 in (25, 625, 4225, 7225):
+        r = int(r2 ** 0.5)
+        circles[r2] = [(x, y) for x in range(-r, r + 1) for y in range(-r, r + 1) if x * x + y * y == r2]
+    tiny = np.array([1e-30, -1e-30, 3e-39, -3e-39, 1.401298464324817e-45, -1.401298464324817e-45, 7e-20, 0.0], F32)
+    while len(out) < 240:
+        pts = circles[(25, 625, 4225, 7225)[len(out) // 2 % 4]]
+        q = np.array([pts[k] for k in rng.choice(len(pts), 4, replace=False)], np.int64) + rng.integers(-300, 300, 2)
+        q = (q.astype(np.float64) * 2.0 ** -7 + 90000.0 * rng.choice([-1, 1], 2)).astype(F32)
+        if M.orient2d(*[(Fraction(float(x)), Fraction(float(y))) for x, y in q[:3]]) == 0:
+            continue
+        assert M.incircle(*[(Fraction(float(x)), Fraction(float(y))) for x, y in q]) == 0     # nothing rounded
+        add(q)
+        A, B = (rng.integers(-300, 300, 2) * 2.0 ** -7 + 90000.0) * rng.choice([-1, 1], 2)
+        abc = np.array([(A, 0), (0, B), (A, B)], F32)[rng.permutation(3)]
+        assert float(abc.max()) in (float(A), float(B), 0.0)                                   # exact in f32
+        add(np.concatenate([abc, tiny[rng.integers(0, len(tiny), 2)].reshape(1, 2)]))
+    return "\n".join(out) + "\n"
+
+
+def parse_cases(text):
     cases = []
-    for r in rows:
+    for r in (line.split() for line in text.splitlines() if line.strip()):
         vals = np.array([int(h, 16) for h in r[1:]], np.uint32).view(F32)
         assert len(vals) == NV[r[0]]
         cases.append((r[0], [Fraction(float(v)) for v in vals]))
     return cases
+
+
+def read_cases():
+    with open(CASES) as f:
+        return parse_cases(f.read())
 
 
 def exact_sign(kind, v):
@@ -112,10 +154,10 @@ def test_committed_cases_are_the_generated_ones():
         assert f.read() == generate_cases()
 
 
-def run_driver(tmp_path, extra, name):
+def run_driver(tmp_path, extra, name, cases=CASES):
     exe = str(tmp_path / name)
     subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", *extra, "-o", exe, SRC], check=True)
-    r = subprocess.run([exe, CASES], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([exe, cases], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     return [tuple(int(t) for t in line.split()) for line in r.stdout.splitlines()]
 
@@ -145,3 +187,19 @@ def test_predicates_against_fractions(tmp_path, expected, flags):
         assert undecided[kind] >= 50 and zeros[kind] >= 30, (kind, undecided, zeros)
         signs = {w for (k, _), w in zip(cases, want) if k == kind}
         assert signs == {-1, 0, 1}
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_incircle_where_the_low_part_of_two_prod_decides(tmp_path):
+    text = generate_lifted_cases()
+    path = tmp_path / "lifted_cases.txt"
+    path.write_text(text)
+    cases = parse_cases(text)
+    want = [exact_sign(k, v) for k, v in cases]
+    got = run_driver(tmp_path, (), "exact_pred_test", str(path))
+    assert len(got) == len(cases) == 240
+    for n, (w, (fs, s)) in enumerate(zip(want, got)):
+        assert s == w and fs in (w, 2), (n, fs, s, w)
+    # exact zeros and both signs, and no row that the filter decides
+    assert want.count(0) >= 120 and want.count(1) >= 30 and want.count(-1) >= 30, [want.count(v) for v in (-1, 0, 1)]
+    assert all(fs == 2 for fs, _ in got)

@@ -120,6 +120,31 @@ def test_host_entry_equals_the_reference(make):
     assert got.dtype == np.int32 and got.shape == ref.shape and got.tobytes() == ref.tobytes()
 
 
+@pytest.mark.parametrize("name,make,_", M.ADVERSARIAL, ids=[a[0] for a in M.ADVERSARIAL])
+def test_host_entry_equals_the_reference_on_adversarial_sets(name, make, _):
+    """the sets of tests/test_mesh_gpu.py, so that the fixtures, the reference's
+    own tie rule (its assert len(win) == 1) and the host twin are checked
+    where there is no device"""
+    xy, ref = M.cached_ref(name, make)
+    assert M.in_range(xy)
+    M.check_delaunay(xy, ref)
+    got = api.delaunay2dHost(xy)
+    assert got.dtype == np.int32 and got.shape == ref.shape and got.tobytes() == ref.tobytes()
+    if name.startswith("lattice_circle_s") or name == "lattice_circle_32045":
+        assert len(xy) in (108, 324) and len(ref) == len(xy) - 2 and (ref[:, 0] == 0).all()     # one fan from vertex 0
+    if name.startswith("dups"):
+        assert len(M.vertices(xy)) < len(xy) and set(got.ravel().tolist()) == set(M.vertices(xy))
+
+
+@pytest.mark.parametrize("make,n,count", M.HULL_COUNTS, ids=[f"{f.__name__}_{n}" for f, n, _ in M.HULL_COUNTS])
+def test_host_entry_at_power_of_two_triangle_counts(make, n, count):
+    xy, ref = M.cached_ref(f"{make.__name__}_{n}", lambda: make(n))
+    assert len(xy) == n and len(ref) == count                      # Euler: the fixture proves itself
+    M.check_delaunay(xy, ref)
+    got = api.delaunay2dHost(xy)
+    assert got.dtype == np.int32 and got.shape == ref.shape and got.tobytes() == ref.tobytes()
+
+
 def test_host_entry_status_codes():
     import ctypes
     from slamhip import _lib as L

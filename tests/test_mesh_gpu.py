@@ -173,6 +173,93 @@ def test_device_pointer_entry(gpu_ctx):
     assert int(d_n.cpu()[0]) == 0
 
 
+@pytest.mark.parametrize("name,make,need", M.ADVERSARIAL, ids=[a[0] for a in M.ADVERSARIAL])
+def test_adversarial_sets_equal_the_reference(gpu_ctx, name, make, need):
+    """more tie members than lanes (the in-lane t1 / t2 / flag updates of apex),
+    duplicates whose first copy is in an earlier pre-pass tile, coordinates at
+    the ends of the range and in the subnormals"""
+    xy, ref = M.cached_ref(name, make)
+    assert M.in_range(xy)
+    got = api.delaunay2d(xy, ctx=gpu_ctx)
+    pred, exact, ties = api.delaunayStats(ctx=gpu_ctx)
+    print(name, "n", len(xy), "T", len(got), "pred", pred, "exact", exact, "ties", ties)
+    same_bytes(got, ref)
+    same_bytes(api.delaunay2d(xy, ctx=gpu_ctx), got)            # a second call: identical bytes
+    same_bytes(api.delaunay2dHost(xy), got)                      # the scene driver's path below 64 points
+    if need == "ties":
+        assert ties > 0 and 0 < exact <= pred
+    elif need == "exact":
+        assert 0 < exact <= pred
+    if name.startswith("dups"):
+        assert len(M.vertices(xy)) < len(xy)
+        assert set(got.ravel().tolist()) == set(M.vertices(xy))  # first copies only, every one of them
+
+
+@pytest.mark.parametrize("make,n,count", M.HULL_COUNTS, ids=[f"{f.__name__}_{n}" for f, n, _ in M.HULL_COUNTS])
+def test_triangle_counts_at_the_sort_edges(gpu_ctx, make, n, count):
+    """T = 255, 256, 257, 512, 513: one padding triple, tri_pad not launched,
+    the first padded size above a tile, the first tri_bitonic_step launch"""
+    xy, ref = M.cached_ref(f"{make.__name__}_{n}", lambda: make(n))
+    assert len(xy) == n and len(ref) == count                    # Euler: the fixture proves itself
+    got = api.delaunay2d(xy, ctx=gpu_ctx)
+    same_bytes(got, ref)
+    same_bytes(api.delaunay2d(xy, ctx=gpu_ctx), got)
+    same_bytes(api.delaunay2dHost(xy), got)
+
+
+def test_scratch_is_reused_across_sizes():
+    """one context: a large call, a tiny one, a tie-heavy one, the large one again"""
+    ctx = slamhip.Context(0)
+    try:
+        big = M.uniform(3000)
+        first = api.delaunay2d(big, ctx=ctx)
+        M.check_delaunay(big, first)
+        small = M.uniform(5)
+        same_bytes(api.delaunay2d(small, ctx=ctx), M.delaunay_ref(small))
+        xy, ref = M.cached_ref("lattice_circle_s7", lambda: M.lattice_circle(seed=7))
+        same_bytes(api.delaunay2d(xy, ctx=ctx), ref)
+        last = api.delaunay2d(big, ctx=ctx)
+        M.check_delaunay(big, last)
+        same_bytes(last, first)
+    finally:
+        ctx.close()
+
+
+def test_device_entry_alignment_and_stream(gpu_ctx):
+    import torch
+    xy = M.uniform(129)
+    ref = M.delaunay_ref(xy)
+    n = len(xy)
+    dev = torch.device("cuda", gpu_ctx.device)
+    flat = torch.zeros(2 * n + 2, dtype=torch.float32, device=dev)
+    assert flat.data_ptr() % 8 == 0
+    flat[1:1 + 2 * n] = torch.from_numpy(xy.reshape(-1)).to(dev)           # the points, 4 bytes past alignment
+    d_xy = torch.from_numpy(xy).to(dev)
+    d_tris = torch.full((2 * n, 3), -7, dtype=torch.int32, device=dev)
+    d_n = torch.full((1,), -7, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)
+    lib = slamhip.lib()
+
+    def call(stream, ptr):
+        return lib.slam_delaunay_2d_dev(gpu_ctx.handle, stream, ctypes.c_void_p(ptr), n,
+                                        ctypes.c_void_p(d_tris.data_ptr()), 2 * n, ctypes.c_void_p(d_n.data_ptr()))
+
+    assert call(None, flat.data_ptr() + 4) == L.SLAM_E_INVALID_ARG
+    L.check(lib.slam_synchronize(gpu_ctx.handle), gpu_ctx.handle)
+    torch.cuda.synchronize(dev)
+    assert int(d_n.cpu()[0]) == -7 and (d_tris.cpu().numpy() == -7).all()  # nothing written
+
+    stream = torch.cuda.Stream(device=dev)
+    assert stream.cuda_stream != 0
+    stream.wait_stream(torch.cuda.current_stream(dev))
+    assert call(ctypes.c_void_p(stream.cuda_stream), d_xy.data_ptr()) == L.SLAM_OK      # it waits for the stream
+    stream.synchronize()
+    assert int(d_n.cpu()[0]) == len(ref)
+    got = d_tris.cpu().numpy()
+    same_bytes(got[:len(ref)].copy(), ref)
+    assert (got[len(ref):] == -7).all()
+
+
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_cpp_host_layer_make_mesh(gpu_ctx, tmp_path):
     """slamhip::makeMesh (host/slamhip.hpp) returns the reference's polygon list
