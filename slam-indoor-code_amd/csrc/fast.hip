@@ -459,8 +459,12 @@ __global__ __launch_bounds__(kFastThreads) void fast_detect(DetectParams p)
 // count <= cap), so that kernels which read it before the host has checked the
 // total (the fused extract + match) never index past the keypoint buffers; the
 // total stays unclipped and the host reports SLAM_E_CAPACITY from it.
-__global__ __launch_bounds__(1024) void fast_finalize(const int* band_cnt, int nframes, int nbands,
-                                                      int* band_pref, int4* frame_info, int* total, int cap)
+// Four waves: a 16-wave workgroup was not placed beside a sift_desc_band workgroup
+// of the other context (2.8 ms in the pipelined step's trace, until the
+// descriptor's tail; 0.16 ms with four), and FAST's emit and the blur wait for it.
+constexpr int kFinalizeThreads = 256;
+__global__ __launch_bounds__(kFinalizeThreads) void fast_finalize(const int* band_cnt, int nframes, int nbands,
+                                                                  int* band_pref, int4* frame_info, int* total, int cap)
 {
     __shared__ int cnt[1024];
     __shared__ int raw[1024];
@@ -468,7 +472,7 @@ __global__ __launch_bounds__(1024) void fast_finalize(const int* band_cnt, int n
     for (int base = 0; base < nframes; base += 1024) {
         // one wave per frame: the band counts 64 at a time, a wave prefix scan
         // for band_pref (the serial per-frame loop was a chain of dependent loads)
-        for (int fl = wave; fl < 1024 && base + fl < nframes; fl += 16) {
+        for (int fl = wave; fl < 1024 && base + fl < nframes; fl += kFinalizeThreads / 64) {
             const int f = base + fl;
             int run = 0, rsum = 0;
             for (int b0 = 0; b0 < nbands; b0 += 64) {
@@ -646,7 +650,7 @@ hipError_t launch_fast_emit(slam_ctx* c, hipStream_t s, int nframes, int w, int 
     if ((e = c->misc.ensure(256)) != hipSuccess) return e;
     if ((e = c->kps.ensure((size_t)cap * sizeof(slam_keypoint))) != hipSuccess) return e;
     if ((e = c->kp_frame.ensure((size_t)cap * sizeof(int))) != hipSuccess) return e;
-    hipLaunchKernelGGL(fast_finalize, dim3(1), dim3(1024), 0, s, c->band_cnt.as<int>(), nframes, nbands,
+    hipLaunchKernelGGL(fast_finalize, dim3(1), dim3(kFinalizeThreads), 0, s, c->band_cnt.as<int>(), nframes, nbands,
                        c->band_pref.as<int>(), c->frame_info.as<int4>(), c->misc.as<int>(), cap);
     EmitParams p;
     p.masks = c->masks.as<uint64_t>(); p.scores = c->scores.as<uint8_t>();

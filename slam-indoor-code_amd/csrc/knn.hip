@@ -870,16 +870,21 @@ __global__ __launch_bounds__(256) void knn_finish(FinishParams p)
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(&p.counts[fr], __popcll(b));
 }
 
-// order-preserving compaction of the ratio-test survivors, one workgroup per frame
-__global__ __launch_bounds__(1024) void knn_compact(const slam_dmatch* rec, const uint8_t* flag, int nq,
-                                                    slam_dmatch* out, int* out_counts, int stride)
+// order-preserving compaction of the ratio-test survivors, one workgroup per frame.
+// Four waves: in the pipelined step this kernel is queued while the other
+// context's sift_desc_band holds every CU, and the next extraction waits behind
+// it.  A 16-wave workgroup was not placed beside a descriptor workgroup (8.5 ms
+// in the trace, until the descriptor's tail), a 4-wave one is (0.06 ms).
+constexpr int kCompactThreads = 256;
+__global__ __launch_bounds__(kCompactThreads) void knn_compact(const slam_dmatch* rec, const uint8_t* flag, int nq,
+                                                               slam_dmatch* out, int* out_counts, int stride)
 {
-    __shared__ int wtot[16];
+    __shared__ int wtot[kCompactThreads / 64];
     __shared__ int running;
     const int fr = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     if (t == 0) running = 0;
     __syncthreads();
-    for (int base = 0; base < nq; base += 1024) {
+    for (int base = 0; base < nq; base += kCompactThreads) {
         const int q = base + t;
         const int f = (q < nq) ? flag[(size_t)fr * nq + q] : 0;
         const uint64_t b = __ballot(f != 0);
@@ -890,7 +895,7 @@ __global__ __launch_bounds__(1024) void knn_compact(const slam_dmatch* rec, cons
         for (int i = 0; i < wave; i++) wb += wtot[i];
         if (f) out[(size_t)fr * stride + wb + below] = rec[(size_t)fr * nq + q];
         __syncthreads();
-        if (t == 0) { int s = 0; for (int i = 0; i < 16; i++) s += wtot[i]; running += s; }
+        if (t == 0) { int s = 0; for (int i = 0; i < kCompactThreads / 64; i++) s += wtot[i]; running += s; }
         __syncthreads();
     }
     if (t == 0) out_counts[fr] = running;
@@ -980,7 +985,7 @@ hipError_t launch_compact(slam_ctx* c, hipStream_t s, const slam_dmatch* rec, co
 {
     (void)c;
     if (nq <= 0 || nframes <= 0) return hipSuccess;
-    hipLaunchKernelGGL(knn_compact, dim3(nframes), dim3(1024), 0, s, rec, flag, nq, out, out_counts, stride);
+    hipLaunchKernelGGL(knn_compact, dim3(nframes), dim3(kCompactThreads), 0, s, rec, flag, nq, out, out_counts, stride);
     return hipGetLastError();
 }
 

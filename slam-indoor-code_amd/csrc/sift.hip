@@ -212,7 +212,7 @@ __global__ __launch_bounds__(kBlurThreads) void sift_blur_grad(BlurGradParams p)
     auto pos_byte = [](float ob) {
         int o0;
         __asm__("v_cvt_flr_i32_f32 %0, %1" : "=v"(o0) : "v"(ob));
-        return (uint32_t)((o0 + 9) * 6);
+        return (uint32_t)((o0 + 9) * kBandSlotCols);
     };
     if (x0 + kBT <= 0 || y0 + kBT <= 0 || x0 >= p.w || y0 >= p.h) {
         // tile outside the image: the border only

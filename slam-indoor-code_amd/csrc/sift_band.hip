@@ -65,31 +65,38 @@ namespace {
 #ifndef SIFT_BAND_WAVES
 #define SIFT_BAND_WAVES 8
 #endif
-#ifndef SIFT_BAND_SLOTCOLS
-#define SIFT_BAND_SLOTCOLS 6
-#endif
 constexpr int kKS = SIFT_BAND_KS;       // window samples per staged chunk
 constexpr int kStride = 2 * kKS + 4;    // stage floats per keypoint ({mw, obin} x kKS; 16-byte rows, b128 conflict-free)
 constexpr int kWaves = SIFT_BAND_WAVES;
 constexpr int kKpW = 32;                // keypoints per wave; lane = keypoint + 32 * dc
 constexpr int kPos = 10;                // slot positions: 0 = left cell's slot 9, 1..9 = slots 0..8
 constexpr int kCols = 5;                // histogram columns 0..4 (4: the 361-degree quirk column)
-// Slots: float index pos * kPosF + col' * 64 + 2 * keypoint + row, col' = 4 - column
-// (col' = 5, column -1, is a junk column: the c0 = -1 samples' column-c0 share,
-// outside the descriptor), row 0 = the band's upper target row r0 + 1... i.e. the
-// pair {row r0, row r0 + 1} of the two rows a band's samples reach.  A lane
+// Slots: float index pos * kPosF + col' * 64 + 2 * keypoint + row, col' = 4 - column,
+// row 0 = the band's upper target row r0 + 1... i.e. the pair {row r0, row r0 + 1}
+// of the two rows a band's samples reach.  A position holds five columns, col'
+// 0..4.  The c0 = -1 samples' column-c0 share (column -1, col' = 5: outside the
+// descriptor, never read) is junk and has no column of its own: col' = 5 of
+// position p is col' = 0 of position p + 1.  col' = 0 is the quirk column, of
+// which only position 0 is read (column 3's slot 9), so junk written at
+// positions 0..9 lands in its positions 1..10: 1..9 are discarded anyway, and
+// position 10 is the kJunkPad floats behind the last position.  17.4 KB per wave
+// instead of 19.6 (139 KB per workgroup) leave a CU 24 KB of LDS for a workgroup
+// of another kernel.  A lane
 // owns one column of a sample's 2 x 2 x 2 cell (dc = 0: column c0 + 1, dc = 1:
 // column c0) and updates its four bins as two 8-byte pairs {row r0, row r0 + 1}
 // at positions p and p + 1: ds_read_b64 / ds_write_b64 with packed f32 adds.
 // Banks: 2 * keypoint (+1) whatever the column and position -- conflict-free
 // for both the 32-lane read groups and the 16-lane write groups.
-constexpr int kPosF = SIFT_BAND_SLOTCOLS * 64;
-static_assert(SIFT_BAND_SLOTCOLS == kCols + 1, "slot columns: the junk column has its own slots");
-// one-row layout of bands -1 and 3 (same memory): pos * kPos1F + col' * 32 + keypoint.
-// The position stride is the pair layout's (half of each position unused): one
-// slot-position byte (gradpos, (floor(obin) + 9) * 6) shifted by 8 addresses both
+constexpr int kPosF = kBandSlotCols * 64;
+static_assert(kBandSlotCols == kCols, "slot columns: the junk column aliases the quirk column's discarded slots");
+constexpr int kJunkPad = 64;            // col' = 5 of position 9
+// one-row layout of bands -1 and 3 (same memory): pos * kPos1F + col' * 32 + keypoint,
+// col' 0..5 (192 of a position's 320 floats: here the junk column has slots of its
+// own).  The position stride is the pair layout's: one slot-position byte (gradpos,
+// (floor(obin) + 9) * kBandSlotCols) shifted by 8 addresses both
 constexpr int kPos1F = kPosF;
-constexpr int kSlots = kPos * kPosF;
+static_assert(6 * 32 <= kPos1F, "one-row layout: six columns per position");
+constexpr int kSlots = kPos * kPosF + kJunkPad;
 constexpr int kStageOff = kSlots;
 constexpr int kKpOff = kStageOff + kKpW * kStride;
 constexpr int kWaveFloats = kKpOff + kKpW;
@@ -97,7 +104,8 @@ constexpr int kMaxChunks = 1024;
 constexpr int kTabCols = 5;              // per chunk: rf, cf, slot offsets of the 32- and 16-keypoint layouts, weight
 constexpr int kRawStride = 129;          // epilogue: one keypoint per lane, odd stride = conflict-free
 static_assert(kKpW * kRawStride <= kKpOff, "epilogue raw buffer must fit below the keypoint offsets");
-static_assert(kWaves * kWaveFloats * 4 <= 160 * 1024, "LDS");
+// one workgroup per CU, and beside it one of fast_detect (19,168 B) or knn_mfma_pk (16,896 B)
+static_assert(kWaves * kWaveFloats * 4 <= 160 * 1024 - 19168, "LDS");
 static_assert(kStageOff % 4 == 0 && kStride % 4 == 0 && kWaveFloats % 4 == 0, "16-byte stage rows");
 
 // the 16-keypoint variant (sift_desc_band4, below): four lanes per keypoint
@@ -139,6 +147,7 @@ struct BandParams {
     int parts_env;                      // SLAMHIP_SIFT_BAND_PARTS: 2 / 4 parts forced (timing), else 0
     float4* split_raw;                  // [slot][row][lane][4]: the parts' finished rows
     int* split_cnt;                     // [slot]: halves arrived (reset to 0 by the second)
+    int* deal;                          // [8]: next full-round job of each XCD range (sift_desc_band only; null: static deal)
 };
 
 typedef float f2v __attribute__((ext_vector_type(2)));
@@ -232,7 +241,19 @@ __global__ __launch_bounds__(64 * kWaves) void sift_desc_band(BandParams p)
     char* lb2 = lb - 9 * kPosF * 4;
     char* lb12 = lb1 - 9 * kPos1F * 4;
     const f2v km2 = {dc ? 1.f : 0.f, dc ? 1.f : 0.f}, kn2 = {dc ? -1.f : 1.f, dc ? -1.f : 1.f};
-    for (int job = wi; job < njobs; job += nw) {
+    // The full rounds' jobs are taken from the XCD range's counter (p.deal, zero at
+    // launch), in order: in the pipelined step a workgroup may find its CU only
+    // when the other context's kNN has drained from it, and dealt statically its
+    // late start would be the whole kernel's late end.  The last, partial round
+    // stays dealt by wave index (the spread and the part-walks above).  Which wave
+    // walks a group does not change the group's result.
+    auto take = [&]() __attribute__((always_inline)) {
+        int j = lane == 0 ? atomicAdd(p.deal + xg, 1) : 0;
+        j = __builtin_amdgcn_readfirstlane(j);
+        return j < full ? j : full + wi;
+    };
+    const bool dyn = p.deal != nullptr && full > 0;
+    for (int job = dyn ? take() : wi; job < njobs; job = dyn && job < full ? take() : job + nw) {
         // rows r_lo..r_hi of the descriptor: 0..3 for a whole walk, else a part's
         int grp = g0 + job, r_lo = 0, r_hi = 3, part = -1;
         if (split && job >= full) {
@@ -302,14 +323,14 @@ __global__ __launch_bounds__(64 * kWaves) void sift_desc_band(BandParams p)
                 if constexpr (kObin == 3) {
                     // the walk's slot position, formed once per keypoint-sample here instead
                     // of on both of its walk lanes: fract(obin) in the record, the byte
-                    // (floor(obin) + 9) * 6 in the row's pad (the position-plane layout)
+                    // (floor(obin) + 9) * kBandSlotCols in the row's pad (the position-plane layout)
                     int oa, ob2;
                     __asm__("v_cvt_flr_i32_f32 %0, %1" : "=v"(oa) : "v"(oba));
                     __asm__("v_cvt_flr_i32_f32 %0, %1" : "=v"(ob2) : "v"(obb));
                     *reinterpret_cast<float4*>(stg + (kPer * it + kl) * kStride + 4 * s2) =
                         make_float4(mwa, mwb, __builtin_amdgcn_fractf(oba), __builtin_amdgcn_fractf(obb));
                     *reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(stg + (kPer * it + kl) * kStride + 2 * kKS) + 2 * s2) =
-                        (uint16_t)(__mul24(oa + 9, 6) | __mul24(ob2 + 9, 6) << 8);
+                        (uint16_t)(__mul24(oa + 9, kBandSlotCols) | __mul24(ob2 + 9, kBandSlotCols) << 8);
                     continue;
                 }
                 if constexpr (kObin < 2) {
@@ -398,7 +419,7 @@ __global__ __launch_bounds__(64 * kWaves) void sift_desc_band(BandParams p)
                 // ob - floor(ob) never rounds up to 1.0, where fract would clamp)
                 float frac;
                 if constexpr (kObin >= 2) {
-                    // stored fract(obin); byte (o0 + 9) * 6 moved to bits 8..15 = (o0 + 9) * 1536
+                    // stored fract(obin); byte (o0 + 9) * kBandSlotCols moved to bits 8..15 = (o0 + 9) * kPosF * 4
                     frac = ob;
                     tp[q] = lb2 + tof[q] + __builtin_amdgcn_perm(0u, pw[q >> 2], 0x0c0c000cu | (uint32_t)(q & 3) << 8);
                 } else {
@@ -529,8 +550,9 @@ __global__ __launch_bounds__(64 * kWaves) void sift_desc_band(BandParams p)
             constexpr int b = decltype(B)::value;
             if constexpr (b == -1) {
                 // row r0 + 1 (descriptor row 0) leaves the one-row layout for the pairs'
-                // first element; the second starts at 0.  The lane moves columns 3 dc ..
-                // 3 dc + 2 of its keypoint (every slot pair is written).
+                // first element; the second starts at 0.  The lane moves col' 3 dc ..
+                // 3 dc + 2 of its keypoint (every slot pair is written; col' = 5 is junk
+                // and lands in the quirk column's discarded slots, like the walk's).
                 float v[3][kPos];
 #pragma unroll
                 for (int c = 0; c < 3; c++)
@@ -548,9 +570,10 @@ __global__ __launch_bounds__(64 * kWaves) void sift_desc_band(BandParams p)
                 wave_sync();
                 if constexpr (b < 2) {
                     // shift: the second element becomes the first, the second restarts at 0
+                    // (the ten positions; the junk pad stays junk)
                     float2* z = reinterpret_cast<float2*>(buf);
-#pragma unroll 6
-                    for (int q = 0; q < kSlots / 128; q++) {
+#pragma unroll 5
+                    for (int q = 0; q < kPos * kPosF / 128; q++) {
                         float2 vv = z[q * 64 + lane];
                         z[q * 64 + lane] = make_float2(vv.y, 0.f);
                     }
@@ -711,7 +734,7 @@ __global__ __launch_bounds__(64 * kWaves) void sift_desc_band(BandParams p)
 }
 
 // ---- sift_desc_band4: 16 keypoints per wave, four lanes per keypoint ----------
-// The band kernel above keeps 32 keypoints' slots per wave (19.6 KB), so the
+// The band kernel above keeps 32 keypoints' slots per wave (17.4 KB), so the
 // LDS holds 8 waves per CU, 2 per SIMD; each wave walks its samples as a chain
 // of slot read-add-writes whose LDS round trips two waves per SIMD do not
 // cover (the LDS array ~55 % busy).  Here a wave holds 16 keypoints (10 KB of
@@ -1403,9 +1426,10 @@ hipError_t launch_sift_desc_band(slam_ctx* c, hipStream_t s, int w, int h, int c
         p.split = 0;
         p.split_raw = nullptr;
         p.split_cnt = nullptr;
+        p.deal = nullptr;
         split_ok = wm && band_split != SLAM_BAND_SPLIT_OFF;
     }
-    // persistent: one 8-wave workgroup per CU (157 KB of LDS; band4: two of 80 KB),
+    // persistent: one 8-wave workgroup per CU (139 KB of LDS; band4: two of 80 KB),
     // a multiple of 8 workgroups for the XCD split
     const bool b4 = sift_band4_enabled();
     int grid = b4 ? 2 * c->cu_count : c->cu_count;
@@ -1427,6 +1451,12 @@ hipError_t launch_sift_desc_band(slam_ctx* c, hipStream_t s, int w, int h, int c
         p.split = band_split;
         p.split_raw = c->sift_split.as<float4>();
         p.split_cnt = c->sift_split_cnt.as<int>();
+    }
+    if (!b4) {
+        // the job counters of the eight XCD ranges, zero at every launch
+        if ((e = c->sift_deal.ensure(8 * sizeof(int))) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(c->sift_deal.p, 0, 8 * sizeof(int), s)) != hipSuccess) return e;
+        p.deal = c->sift_deal.as<int>();
     }
     prof_begin(c, 1, s);
     if (!b4 && obin == 1 && m.neg && c->sift_colw_valid &&

@@ -51,6 +51,10 @@ struct SiftConsts {
 // parity is preserved (sift_tab's 16-byte pair loads).
 constexpr int kGradPad = 48;
 __host__ __device__ __forceinline__ int grad_pitch(int w) { return (w + 2 * kGradPad + 7) & ~7; }
+// Slot columns per orientation position of sift_desc_band (64 floats each); the
+// position byte plane of sift_blur_grad (obin 2) stores position * kBandSlotCols,
+// which shifted by 8 is the position's byte offset in the slots.
+constexpr int kBandSlotCols = 5;
 
 // XCD-contiguous tile order for a 3-D grid of image tiles (x, y, frame):
 // workgroups are dealt round-robin over the 8 XCDs by linear id, so raster-
@@ -252,6 +256,7 @@ struct slam_ctx {
     slamhip::DevBuf sift_band_buf;
     slamhip::DevBuf sift_split;          // sift_desc_band split tail: the halves' rows
     slamhip::DevBuf sift_split_cnt;      // ... and their arrival counters (zero between launches)
+    slamhip::DevBuf sift_deal;           // sift_desc_band: the XCD ranges' job counters (zeroed before each launch)
     bool sift_band_valid = false;
     float sift_band_angle = 0.f, sift_band_size = 0.f;
     slamhip::SiftBandMeta sift_band;

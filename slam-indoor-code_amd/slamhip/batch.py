@@ -578,7 +578,8 @@ class PipelinedScan:
     after search k's kNN (no two large kernels share the chip), "desc_end"
     when search k's descriptor kernel has finished (beside its kNN), or
     "desc_start" when it has been reached (its workgroups hold the CUs; the
-    next gray / FAST / blur take CUs as its tail frees them).  Results are the
+    next FAST fits beside them, the blur takes CUs as its tail frees them;
+    DESIGN.md section 9a).  Results are the
     same in every mode: each context's own work stays in its stream order."""
 
     OVERLAPS = {"desc_start": L.STAGE_DESC_START, "desc_end": L.STAGE_DESC_END}
