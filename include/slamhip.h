@@ -371,7 +371,11 @@ int slam_batch_fast_reused(const slam_ctx* ctx);
 /* match every extracted frame (train) against one query descriptor set that is
  * already in device memory in the context's internal format (see
  * slam_batch_export_desc).  match_counts (host, nframes) receives the ratio-test
- * survivor counts used by the selection rule. */
+ * survivor counts used by the selection rule.
+ * Precondition (not checked): the batch path always ranks SIFT L2 candidates
+ * with packed keys, which need d^2 < 2^21 - 1.  Extracted descriptors have a
+ * norm of at most 518, so every query descriptor must have a norm of at most
+ * 518 too, as slam_batch_export_desc produces. */
 int slam_batch_match(slam_ctx* ctx, void* stream, const void* d_query, int nq,
                      int norm, double ratio, int32_t* match_counts);
 
@@ -515,6 +519,20 @@ enum slam_sift_kernel { SLAM_SIFT_KERNEL_AUTO = 0, SLAM_SIFT_KERNEL_BAND = 1, SL
 int slam_set_option(slam_ctx* ctx, int option, int value);
 /* the SLAM_SIFT_KERNEL_* that ran the context's last SIFT descriptor launch (0 before any) */
 int slam_last_sift_kernel(const slam_ctx* ctx);
+
+/* which kNN kernel the context's last matcher launch ran (slam_knn2, slam_match,
+ * slam_batch_match and their fused / asynchronous forms).  *mode: the key mode
+ * (SLAM_KNN_MODE_*), *tsplit: the train-set split count of the launch (grid z),
+ * *variant: the template instance (SLAM_KNN_VARIANT_*), with
+ * SLAM_KNN_VARIANT_XCD or'ed in when the blocks ran in XCD-contiguous order.
+ * Any pointer may be NULL.  Returns SLAM_OK, or SLAM_E_INVALID_ARG before the
+ * context's first launch.  For tests: the choice of kernel is internal. */
+enum slam_knn_mode { SLAM_KNN_MODE_L2 = 0, SLAM_KNN_MODE_SQRT = 2, SLAM_KNN_MODE_L2_PACKED = 3,
+                     SLAM_KNN_MODE_HAMMING_PACKED = 4, SLAM_KNN_MODE_L1_PACKED = 5 };
+enum slam_knn_variant { SLAM_KNN_VARIANT_NONE = 0, SLAM_KNN_VARIANT_MFMA = 1, SLAM_KNN_VARIANT_MFMA_PK_QT2 = 2,
+                        SLAM_KNN_VARIANT_MFMA_PK_QT1 = 3, SLAM_KNN_VARIANT_PIPE_QT2 = 4,
+                        SLAM_KNN_VARIANT_PIPE_QT1 = 5, SLAM_KNN_VARIANT_L1 = 6, SLAM_KNN_VARIANT_XCD = 0x100 };
+int slam_last_knn_launch(const slam_ctx* ctx, int* mode, int* tsplit, int* variant);
 
 /* ---- profiling hooks (bench.py) ---------------------------------------------- */
 /* average duration (ms) of the last batch's launches of one kernel family,

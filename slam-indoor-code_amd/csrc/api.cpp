@@ -1459,6 +1459,15 @@ int slam_mesh_filter(const float* pts, int n, const int32_t* tris, int n_tris, d
 
 int slam_last_sift_kernel(const slam_ctx* c) { return c ? c->last_sift_kernel : SLAM_E_INVALID_ARG; }
 
+int slam_last_knn_launch(const slam_ctx* c, int* mode, int* tsplit, int* variant)
+{
+    if (!c || c->last_knn_mode < 0) return SLAM_E_INVALID_ARG;
+    if (mode) *mode = c->last_knn_mode;
+    if (tsplit) *tsplit = c->last_knn_tsplit;
+    if (variant) *variant = c->last_knn_variant;
+    return SLAM_OK;
+}
+
 int slam_batch_get_matches(slam_ctx* c, int frame, slam_dmatch* out, int cap, int* n)
 {
     if (!c || !n || frame < 0 || frame >= c->batch.nframes || !c->batch.have_matches) return SLAM_E_INVALID_ARG;

@@ -944,23 +944,41 @@ hipError_t launch_knn(slam_ctx* c, hipStream_t s, int kb, const void* q, const i
     const bool qt1 = kb == 128 && mode == MODE_L2P && knn_pipe_mode() == 3;     // control: knn_mfma_pk, QT 1
     const int qblk = (pipe1 || qt1) ? 128 : (kb == 128 && mode == MODE_L2P) ? KNN_NTH / 2 * KNN_QT : 256;
     dim3 grid((nq + qblk - 1) / qblk, nframes, tsplit);
+    // which instance runs, for slam_last_knn_launch (tests assert the kernel they were written for)
+    constexpr int kPkVariant = KNN_QT == 1 ? SLAM_KNN_VARIANT_MFMA_PK_QT1 : SLAM_KNN_VARIANT_MFMA_PK_QT2;
+    constexpr int kPipeVariant = KNN_QT == 1 ? SLAM_KNN_VARIANT_PIPE_QT1 : SLAM_KNN_VARIANT_PIPE_QT2;
+    const int xbit = kxcd ? SLAM_KNN_VARIANT_XCD : 0;      // only knn_mfma_pk reads p.xcd
+    int variant = SLAM_KNN_VARIANT_NONE;
     prof_begin(c, 2, s);
-    if (kb == 128 && mode == MODE_L2) hipLaunchKernelGGL((knn_mfma<128, MODE_L2, true>), grid, dim3(256), 0, s, p);
-    else if (kb == 128 && mode == MODE_SQRT) hipLaunchKernelGGL((knn_mfma<128, MODE_SQRT, true>), grid, dim3(256), 0, s, p);
-    else if (pipe1)
+    if (kb == 128 && mode == MODE_L2) {
+        variant = SLAM_KNN_VARIANT_MFMA;
+        hipLaunchKernelGGL((knn_mfma<128, MODE_L2, true>), grid, dim3(256), 0, s, p);
+    } else if (kb == 128 && mode == MODE_SQRT) {
+        variant = SLAM_KNN_VARIANT_MFMA;
+        hipLaunchKernelGGL((knn_mfma<128, MODE_SQRT, true>), grid, dim3(256), 0, s, p);
+    } else if (pipe1) {
+        variant = SLAM_KNN_VARIANT_PIPE_QT1;
         hipLaunchKernelGGL((knn_pipe<1, 4, false>), grid, dim3(256), 0, s, p);
-    else if (qt1)
+    } else if (qt1) {
+        variant = SLAM_KNN_VARIANT_MFMA_PK_QT1 | xbit;
         hipLaunchKernelGGL((knn_mfma_pk<128, false, 1, 4>), grid, dim3(256), 0, s, p);
-    else if (kb == 128 && mode == MODE_L2P && knn_pipe_enabled())
+    } else if (kb == 128 && mode == MODE_L2P && knn_pipe_enabled()) {
+        variant = kPipeVariant;
         hipLaunchKernelGGL((knn_pipe<KNN_QT, KNN_PIPE_MINB, false>), grid, dim3(256), 0, s, p);
-    else if (kb == kOrbExpBytes && mode == MODE_HAMP && knn_pipe_enabled())
+    } else if (kb == kOrbExpBytes && mode == MODE_HAMP && knn_pipe_enabled()) {
+        variant = SLAM_KNN_VARIANT_PIPE_QT2;
         hipLaunchKernelGGL((knn_pipe<2, KNN_PIPE_MINB, true>), grid, dim3(256), 0, s, p);
-    else if (kb == 128 && mode == MODE_L2P)
+    } else if (kb == 128 && mode == MODE_L2P) {
+        variant = kPkVariant | xbit;
         hipLaunchKernelGGL((knn_mfma_pk<128, false, KNN_QT, KNN_MINB, KNN_NTH>), grid, dim3(KNN_NTH), 0, s, p);
-    else if (kb == kOrbExpBytes && mode == MODE_HAMP) hipLaunchKernelGGL((knn_mfma_pk<kOrbExpBytes, true, 2, 4>), grid, dim3(256), 0, s, p);
-    else if (kb == 128 && mode == MODE_L1P)
+    } else if (kb == kOrbExpBytes && mode == MODE_HAMP) {
+        variant = SLAM_KNN_VARIANT_MFMA_PK_QT2 | xbit;
+        hipLaunchKernelGGL((knn_mfma_pk<kOrbExpBytes, true, 2, 4>), grid, dim3(256), 0, s, p);
+    } else if (kb == 128 && mode == MODE_L1P) {
+        variant = SLAM_KNN_VARIANT_L1;
         hipLaunchKernelGGL((knn_l1<2>), dim3((nq + 511) / 512, nframes, tsplit), dim3(256), 0, s, p);
-    else { prof_end(c, 2, s); return hipErrorInvalidValue; }
+    } else { prof_end(c, 2, s); return hipErrorInvalidValue; }
+    c->last_knn_mode = mode; c->last_knn_tsplit = tsplit; c->last_knn_variant = variant;
     prof_end(c, 2, s);
     return hipGetLastError();
 }

@@ -15,7 +15,7 @@ from ._lib import (DMATCH_DTYPE, EMPTY_BATCH, FRAME_NOT_FOUND, KEYPOINT_DTYPE, L
 from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_rmse, bundle_adjust_arrays,
                   bundleAdjustment, default_context, extractDescriptor, fastExtractor, getGoodMatches,
                   estimateTransformation, reconstruct, siftDetectAndCompute, siftDetectAndComputeBatch, SiftBatch, solvePnPRansac,
-                  getMatcherTypeIndex, knnMatch2, loss_from_config, matchFeatures, matchFramesPairFeatures,
+                  getMatcherTypeIndex, knnMatch2, lastKnnLaunch, loss_from_config, matchFeatures, matchFramesPairFeatures,
                   rodrigues_to_matrix, rodrigues_to_vector, selectGoodFrame, synth_frames,
                   SYNTH_DRIFT, SYNTH_STEADY, synth_frames_dev,
                   clusterizePoints, clusterLabels, getBestFittingPlaneByPoints, planeMoments, projectToPlane,

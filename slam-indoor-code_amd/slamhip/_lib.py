@@ -34,7 +34,11 @@ OPT_FAST_REUSE = 4
 PNP_SUMS_ORDERED, PNP_SUMS_PAIRWISE = 0, 1
 BAND_SPLIT_OFF, BAND_SPLIT_AUTO, BAND_SPLIT_ALL, BAND_SPLIT_ALL4 = 0, 1, 2, 3
 STAGE_DESC_START, STAGE_DESC_END = 0, 1     # slam_order_after_stage
-SIFT_KERNEL_AUTO, SIFT_KERNEL_BAND, SIFT_KERNEL_TAB, SIFT_KERNEL_GENERAL, SIFT_KERNEL_COLS, SIFT_KERNEL_COLW = 0, 1, 2, 3, 4, 5
+KNN_MODE_L2, KNN_MODE_SQRT, KNN_MODE_L2_PACKED, KNN_MODE_HAMMING_PACKED, KNN_MODE_L1_PACKED = 0, 2, 3, 4, 5
+(KNN_VARIANT_MFMA, KNN_VARIANT_MFMA_PK_QT2, KNN_VARIANT_MFMA_PK_QT1, KNN_VARIANT_PIPE_QT2, KNN_VARIANT_PIPE_QT1,
+ KNN_VARIANT_L1) = range(1, 7)
+KNN_VARIANT_XCD = 0x100
+SIFT_KERNEL_AUTO, SIFT_KERNEL_BAND,SIFT_KERNEL_TAB, SIFT_KERNEL_GENERAL, SIFT_KERNEL_COLS, SIFT_KERNEL_COLW = 0, 1, 2, 3, 4, 5
 
 # byte-identical to cv::KeyPoint / cv::DMatch
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
@@ -100,6 +104,7 @@ SIGNATURES = {
     "slam_set_option": (_I, [_P, _I, _I]),
     "slam_batch_fast_reused": (_I, [_P]),
     "slam_last_sift_kernel": (_I, [_P]),
+    "slam_last_knn_launch": (_I, [_P, _P, _P, _P]),
     "slam_profile_enable": (_I, [_P, _I]),
     "slam_profile_read": (_I, [_P, _I, _P, _P]),
     "slam_synth_frames": (_I, [_I, _I, _I, _I, _U64, _P]),

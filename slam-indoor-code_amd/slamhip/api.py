@@ -303,6 +303,15 @@ def knnMatch2(queryDescriptors, trainDescriptors, matcherType, norm=L.NORM_DEFAU
     return idx, dist
 
 
+def lastKnnLaunch(ctx=None):
+    """(mode, tsplit, variant) of the context's last kNN launch (slam_last_knn_launch):
+    L.KNN_MODE_*, the train-set split count, L.KNN_VARIANT_* (| L.KNN_VARIANT_XCD)."""
+    c = _ctx(ctx)
+    mode, tsplit, variant = ctypes.c_int(-1), ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().slam_last_knn_launch(c, ctypes.byref(mode), ctypes.byref(tsplit), ctypes.byref(variant)), c)
+    return mode.value, tsplit.value, variant.value
+
+
 def getGoodMatches(idx, dist, knnMatcherDistance):
     """featureMatchingCommon.cpp:37-50 on knnMatch2 output (query order)."""
     ok = (idx[:, 0] >= 0) & (idx[:, 1] >= 0)
