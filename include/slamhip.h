@@ -483,6 +483,33 @@ int slam_order_after(slam_ctx* ctx, void* waiter, void* stream);
 #define SLAM_STAGE_DESC_END 1
 int slam_order_after_stage(slam_ctx* ctx, void* waiter, int stage);
 
+/* ---- undistortion ------------------------------------------------------------- */
+/* cv::undistort(src, dst, K, D, newK) (OpenCV 4.8, scalar path, uncontracted
+ * f64 map; INTER_LINEAR, BORDER_CONSTANT 0) at the seam the reference marks at
+ * batch.cpp:244 ("here can be undistortion"), between getNextFrame and
+ * fastExtractor.  K: 3x3 row-major; dist: ndist = 4, 5, 8 or 12 doubles in the
+ * order k1 k2 p1 p2 [k3 [k4 k5 k6 [s1 s2 s3 s4]]] (the calibration file's DC,
+ * IOmisc.cpp:68-76); newK: 3x3 or NULL (= K).  ndist 14 (the tilt model):
+ * SLAM_E_UNSUPPORTED; any other count, or a singular newK: SLAM_E_INVALID_ARG.
+ * The fixed-point map (CV_16SC2 + CV_16UC1, built in cv::undistort's stripes)
+ * is computed on the device once per (K, newK, D, w, h) and kept in the context.
+ *
+ * slam_undistort_batch (cv::undistort per frame, batch.cpp:244): nframes packed
+ * frames in device memory (n x h x w x channels, channels 1 or 3) on `stream`
+ * (NULL = the context stream), no host sync.  Source and destination must not
+ * overlap (SLAM_E_INVALID_ARG); nframes == 0 succeeds without a launch. */
+int slam_undistort_batch(slam_ctx* ctx, void* stream, const uint8_t* d_src, uint8_t* d_dst, int nframes, int w,
+                         int h, int channels, const double* K, const double* dist, int ndist, const double* newK);
+/* cv::undistort of one frame in host memory (batch.cpp:244), any row stride on
+ * either side */
+int slam_undistort(slam_ctx* ctx, const uint8_t* img, int w, int h, size_t step, int channels, const double* K,
+                   const double* dist, int ndist, const double* newK, uint8_t* out, size_t out_step);
+/* the cached map of cv::undistort (batch.cpp:244) to host memory, for callers
+ * that remap themselves and for the tests: xy = h*w*2 (source x, y as shorts),
+ * frac = h*w ((fy << 5) | fx, 5 bits each) */
+int slam_undistort_map(slam_ctx* ctx, int w, int h, const double* K, const double* dist, int ndist,
+                       const double* newK, int16_t* xy, uint16_t* frac);
+
 /* ---- options ------------------------------------------------------------------ */
 /* Per-context choices; all but SLAM_OPT_PNP_SUMS (below) never change results.  SLAM_OPT_SIFT_KERNEL picks the
  * kernel for SIFT descriptors of keypoints sharing one angle and size (FAST

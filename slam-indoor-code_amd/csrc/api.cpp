@@ -418,7 +418,8 @@ void slam_destroy(slam_ctx* c)
                       &c->desc_norm, &c->desc_exp, &c->query_norm, &c->knn_part, &c->match_rec, &c->match_flag,
                       &c->match_cnt, &c->match_out, &c->frames_in, &c->qbuf, &c->tbuf, &c->misc, &c->ba_obs,
                       &c->ba_par, &c->ba_jac, &c->ba_red, &c->ba_S, &c->ba_aux, &c->sd_pyr, &c->sd_cand,
-                      &c->sd_kps, &c->sd_kpc, &c->sift_tab, &c->sift_band_buf, &c->sift_cols_buf, &c->sift_cols_park, &c->sift_colw_buf, &c->sift_split, &c->sift_split_cnt, &c->sift_deal, &c->geom, &c->cluster, &c->delaunay};
+                      &c->sd_kps, &c->sd_kpc, &c->sift_tab, &c->sift_band_buf, &c->sift_cols_buf, &c->sift_cols_park, &c->sift_colw_buf, &c->sift_split, &c->sift_split_cnt, &c->sift_deal, &c->geom, &c->cluster, &c->delaunay,
+                      &c->undist_xy, &c->undist_frac, &c->undist_out};
     for (DevBuf* b : bufs) b->release();
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->ev_up) (void)hipEventDestroy(c->ev_up);
@@ -433,6 +434,7 @@ void slam_destroy(slam_ctx* c)
     for (auto& f : c->prof)
         for (hipEvent_t e : f.ev) (void)hipEventDestroy(e);
     if (c->ev_sync) (void)hipEventDestroy(c->ev_sync);
+    if (c->undist_ev) (void)hipEventDestroy(c->undist_ev);
     (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1189,6 +1191,63 @@ int slam_batch_finish(slam_ctx* c, int32_t* kp_counts, int32_t* match_counts)
         else for (int f = 0; f < done.nframes; f++) match_counts[f] = 0;
     }
     return SLAM_OK;
+}
+
+// ---- cv::undistort at the batch.cpp:244 seam (undistort.hip) ----
+
+int slam_undistort_batch(slam_ctx* c, void* stream, const uint8_t* d_src, uint8_t* d_dst, int nframes, int w, int h,
+                         int channels, const double* K, const double* dist, int ndist, const double* newK)
+{
+    if (!c) return SLAM_E_INVALID_ARG;
+    if (nframes < 0 || (channels != 1 && channels != 3))
+        return set_err(c, SLAM_E_INVALID_ARG, "undistort: frames are packed 8-bit with 1 or 3 channels");
+    if (nframes > 65535 * kUndistFrames) return set_err(c, SLAM_E_UNSUPPORTED, "undistort: too many frames in one call");
+    if (nframes == 0) return SLAM_OK;   // nothing to do: no map build, no launch
+    SLAM_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (int rc = undist_prepare(c, s, w, h, K, dist, ndist, newK)) return rc;
+    if (!d_src || !d_dst) return set_err(c, SLAM_E_INVALID_ARG, "undistort: null frames");
+    const size_t bytes = (size_t)w * h * channels * nframes;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_src), b = reinterpret_cast<uintptr_t>(d_dst);
+    if (a < b + bytes && b < a + bytes)
+        return set_err(c, SLAM_E_INVALID_ARG, "undistort: source and destination frames overlap");
+    SLAM_HIP(c, launch_undist_remap(c, s, d_src, d_dst, nframes, w, h, channels));
+    return undist_mark(c, s);
+}
+
+int slam_undistort(slam_ctx* c, const uint8_t* img, int w, int h, size_t step, int channels, const double* K,
+                   const double* dist, int ndist, const double* newK, uint8_t* out, size_t out_step)
+{
+    if (!c) return SLAM_E_INVALID_ARG;
+    if (int rc = async_guard(c)) return rc;
+    if (!img || !out || (channels != 1 && channels != 3) || !valid_image(w, h, step, channels) ||
+        out_step < (size_t)w * channels)
+        return set_err(c, SLAM_E_INVALID_ARG, "undistort: an 8-bit image with 1 or 3 channels and an output of its size");
+    SLAM_HIP(c, hipSetDevice(c->device));
+    if (int rc = undist_prepare(c, c->stream, w, h, K, dist, ndist, newK)) return rc;
+    const uint8_t* dimg = nullptr;
+    size_t dstep = 0;
+    if (int rc = upload_image(c, img, w, h, step, channels, &dimg, &dstep)) return rc;
+    const size_t row = (size_t)w * channels;
+    SLAM_HIP(c, c->undist_out.ensure(row * h));
+    SLAM_HIP(c, launch_undist_remap(c, c->stream, dimg, c->undist_out.as<uint8_t>(), 1, w, h, channels));
+    if (int rc = undist_mark(c, c->stream)) return rc;
+    SLAM_HIP(c, hipMemcpy2DAsync(out, out_step, c->undist_out.p, row, row, h, hipMemcpyDeviceToHost, c->stream));
+    return stream_sync(c, c->stream);
+}
+
+int slam_undistort_map(slam_ctx* c, int w, int h, const double* K, const double* dist, int ndist, const double* newK,
+                       int16_t* xy, uint16_t* frac)
+{
+    if (!c) return SLAM_E_INVALID_ARG;
+    if (!xy || !frac) return set_err(c, SLAM_E_INVALID_ARG, "undistort: null map output");
+    SLAM_HIP(c, hipSetDevice(c->device));
+    if (int rc = undist_prepare(c, c->stream, w, h, K, dist, ndist, newK)) return rc;
+    const size_t n = (size_t)w * h;
+    SLAM_HIP(c, hipMemcpyAsync(xy, c->undist_xy.p, n * 2 * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    SLAM_HIP(c, hipMemcpyAsync(frac, c->undist_frac.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = undist_mark(c, c->stream)) return rc;
+    return stream_sync(c, c->stream);
 }
 
 void* slam_context_stream(slam_ctx* c) { return c ? (void*)c->stream : nullptr; }

@@ -34,6 +34,9 @@ constexpr int kOrbEdge = 31;           // ORB edgeThreshold, runByImageBorder
 
 // FAST tiles: 64 columns (one wave, one ballot per row) x 16 rows
 constexpr int kFastTileW = 64, kFastTileH = 16;
+// undist_remap (undistort.hip): a workgroup owns one destination tile of
+// kUndistTileW x kUndistTileH pixels and loops over up to kUndistFrames frames
+constexpr int kUndistTileW = 128, kUndistTileH = 8, kUndistFrames = 8;
 
 struct SiftConsts {
     float gauss[16];   // 13-tap kernel of GaussianBlur(sigma = sig_diff)
@@ -270,6 +273,16 @@ struct slam_ctx {
     bool sift_colw_valid = false;
     slamhip::SiftColwMeta sift_colw;
 
+    // undistortion map of one (K, newK, D, w, h) (undistort.hip): CV_16SC2 + CV_16UC1
+    slamhip::DevBuf undist_xy, undist_frac;
+    slamhip::DevBuf undist_out;           // slam_undistort: the device result of a host frame
+    bool undist_valid = false;
+    double undist_key[30] = {};           // K, newK (K when absent), the 12 coefficients
+    int undist_w = 0, undist_h = 0;
+    bool undist_used = false;             // undist_ev has been recorded
+    hipStream_t undist_stream = nullptr;  // the stream that last built or read the map
+    hipEvent_t undist_ev = nullptr;       // ... and the end of that work on it
+
     bool prof_on = false;
     slamhip::ProfFamily prof[8];
     // slam_set_option: which SIFT descriptor kernel runs (all bit-identical)
@@ -436,6 +449,17 @@ int ransac_update_iters(double p, double ep, int modelPoints, int maxIters);
 int pnp_ransac(slam_ctx* c, const float* op, const float* ip, int n, const double* K, int iterations,
                float reproj, double confidence, double* rvec, double* tvec, uint8_t* mask, int* ninliers,
                int* found);
+
+// ---- undistortion (undistort.hip) ----
+// validates the camera model and makes the context's cached map that of
+// (K, newK, D, w, h), building it on s when anything changed; returns a SLAM_* code
+int undist_prepare(slam_ctx* c, hipStream_t s, int w, int h, const double* K, const double* dist, int ndist,
+                   const double* newK);
+// records the end of the map's use on s (after the last launch that reads it)
+int undist_mark(slam_ctx* c, hipStream_t s);
+// remap of nframes packed frames (n x h x w x channels, channels 1 or 3) through the cached map
+hipError_t launch_undist_remap(slam_ctx* c, hipStream_t s, const uint8_t* src, uint8_t* dst, int nframes, int w, int h,
+                               int channels);
 
 // ---- BA (ba.hip) ----
 int ba_solve(slam_ctx* c, double* K4, int nframes, double* ext6, int npoints, double* pts3, int nobs,

@@ -19,7 +19,8 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
                   rodrigues_to_matrix, rodrigues_to_vector, selectGoodFrame, synth_frames,
                   SYNTH_DRIFT, SYNTH_STEADY, synth_frames_dev,
                   clusterizePoints, clusterLabels, getBestFittingPlaneByPoints, planeMoments, projectToPlane,
-                  delaunay2d, delaunay2dHost, delaunayStats, delaunayPredicates, meshFilter)
+                  delaunay2d, delaunay2dHost, delaunayStats, delaunayPredicates, meshFilter,
+                  load_calibration, undistort, undistortBatch, undistortMap)
 from .config import ConfigError, ConfigService, reference_example
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -123,6 +123,9 @@ SIGNATURES = {
     "slam_delaunay_predicates": (_I, [_P, _P, _P, _I, _P, _P]),
     "slam_delaunay_2d_host": (_I, [_P, _I, _P, _I, _P]),
     "slam_mesh_filter": (_I, [_P, _I, _P, _I, _D, _P, _P]),
+    "slam_undistort_batch": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "slam_undistort": (_I, [_P, _P, _I, _I, _SZ, _I, _P, _P, _I, _P, _P, _SZ]),
+    "slam_undistort_map": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P]),
 }
 
 _lib = None

@@ -635,6 +635,116 @@ def meshFilter(points, tris, max_size=MESH_MAX_SIZE):
     return out[:kept.value].copy()
 
 
+# ---- calibration file and undistortion (the batch.cpp:244 seam) ----------------
+
+def load_calibration(path, key="K"):
+    """loadMatrixFromXML (IOmisc.cpp:80-88): the matrix `key` of an OpenCV XML
+    storage as float64.  load_calibration(path) is the camera matrix K that
+    defineCalibrationMatrix reads; "DC" the distortion coefficients that
+    saveCalibParametersToXML writes beside it (IOmisc.cpp:68-76).  Reads
+    opencv-matrix nodes of doubles: <dt> "d", or "<n>d" for n channels, which
+    become n columns per element (R, 13x1 of "3d": 13 x 3).  A missing key raises
+    KeyError."""
+    import xml.etree.ElementTree as ET
+    node = ET.parse(path).getroot().find(key)
+    if node is None:
+        raise KeyError(f"{path}: no matrix {key!r}")
+    if node.get("type_id") != "opencv-matrix":
+        raise ValueError(f"{path}: {key!r} is not an opencv-matrix")
+    rows, cols = int(node.findtext("rows")), int(node.findtext("cols"))
+    dt = node.findtext("dt").strip().strip('"')
+    if not dt.endswith("d") or (dt[:-1] and not dt[:-1].isdigit()):
+        raise ValueError(f"{path}: {key!r} has element type {dt!r}; only doubles are read")
+    ch = int(dt[:-1]) if dt[:-1] else 1
+    data = np.array([float(v) for v in node.findtext("data").split()], np.float64)
+    if data.size != rows * cols * ch:
+        raise ValueError(f"{path}: {key!r} holds {data.size} values, not {rows}x{cols}x{ch}")
+    return data.reshape(rows, cols * ch)
+
+
+def _camera(K, dist, newK):
+    K = np.ascontiguousarray(K, np.float64).reshape(-1)
+    if K.size != 9:
+        raise ValueError("K is 3x3")
+    d = np.ascontiguousarray(dist, np.float64).reshape(-1)
+    n = None
+    if newK is not None:
+        n = np.ascontiguousarray(newK, np.float64).reshape(-1)
+        if n.size != 9:
+            raise ValueError("newK is 3x3")
+    return K, d, n
+
+
+def undistortMap(w, h, K, dist, newK=None, ctx=None):
+    """the fixed-point map of cv::undistort(src, dst, K, dist, newK) for w x h
+    frames (slam_undistort_map): xy (h, w, 2) int16 source x, y and frac (h, w)
+    uint16, (fy << 5) | fx.  Built on the device, cached in the context."""
+    c = _ctx(ctx)
+    K, d, n = _camera(K, dist, newK)
+    xy = np.empty((h, w, 2), np.int16)
+    frac = np.empty((h, w), np.uint16)
+    check(lib().slam_undistort_map(c, int(w), int(h), ptr(K), ptr(d), d.size, ptr(n), ptr(xy), ptr(frac)), c)
+    return xy, frac
+
+
+def undistort(frame, K, dist, newK=None, ctx=None):
+    """cv::undistort(frame, out, K, dist, newK) of an 8-bit gray or BGR frame in
+    host memory (slam_undistort); the seam the reference marks at batch.cpp:244.
+    Rows may be strided (a column range of a wider image)."""
+    c = _ctx(ctx)
+    a = np.asarray(frame)
+    if a.dtype != np.uint8:
+        raise TypeError("frames are 8-bit (CV_8UC1/3)")
+    if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
+        raise ValueError("frame must be HxW or HxWx3 (BGR)")
+    ch = 1 if a.ndim == 2 else 3
+    if a.strides[1:] != ((1,) if ch == 1 else (3, 1)) or a.strides[0] < a.shape[1] * ch:
+        a = np.ascontiguousarray(a)
+    K, d, n = _camera(K, dist, newK)
+    out = np.empty(a.shape, np.uint8)
+    h, w = a.shape[:2]
+    check(lib().slam_undistort(c, ptr(a), w, h, a.strides[0], ch, ptr(K), ptr(d), d.size, ptr(n), ptr(out),
+                               out.strides[0]), c)
+    return out
+
+
+def undistortBatch(frames, K, dist, newK=None, ctx=None, out=None, stream=None):
+    """cv::undistort of n frames resident in HBM in one launch
+    (slam_undistort_batch): `frames` a contiguous torch uint8 tensor (n, h, w, 3)
+    or (n, h, w); the result goes to `out` (same shape, no overlap) or a new
+    tensor.  No host sync.  stream: a HIP stream handle the caller orders
+    itself; by default the launch goes to the context's stream, after what
+    torch's current stream holds so far (the frames' producer) and before what
+    it is given later (the result's consumers), both by device-side waits."""
+    import torch
+    ctx = ctx or default_context()
+    if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or (frames.dim() == 4 and frames.shape[3] != 3):
+        raise ValueError("frames: uint8 (n, h, w) or (n, h, w, 3)")
+    if not frames.is_contiguous():
+        frames = frames.contiguous()
+    if out is None:
+        out = torch.empty_like(frames)
+    if not out.is_contiguous() or out.shape != frames.shape or out.dtype != torch.uint8:
+        raise ValueError("out: a contiguous uint8 tensor of the frames' shape")
+    K, d, n = _camera(K, dist, newK)
+    own = stream is None
+    if own:
+        # torch's current stream may be the legacy default stream, whose handle
+        # (NULL) the C ABI reads as "the context's stream": run there, ordered
+        # against the current stream on both sides
+        cur = torch.cuda.current_stream(frames.device)
+        ready = torch.cuda.Event()
+        ready.record(cur)
+        torch.cuda.ExternalStream(lib().slam_context_stream(ctx.handle), device=frames.device).wait_event(ready)
+    nf, h, w = frames.shape[:3]
+    check(lib().slam_undistort_batch(ctx.handle, None if own else stream, ctypes.c_void_p(frames.data_ptr()),
+                                     ctypes.c_void_p(out.data_ptr()), int(nf), int(w), int(h),
+                                     1 if frames.dim() == 3 else 3, ptr(K), ptr(d), d.size, ptr(n)), ctx.handle)
+    if own:
+        check(lib().slam_order_after(ctx.handle, ctypes.c_void_p(cur.cuda_stream), None), ctx.handle)
+    return out
+
+
 SYNTH_DRIFT, SYNTH_STEADY = 0, 1
 
 

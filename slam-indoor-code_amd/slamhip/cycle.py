@@ -148,6 +148,22 @@ class GpuOps:
         r.dev = dev
         return r
 
+    def undistort(self, frame, K, dist, newK=None):
+        """cv::undistort of a frame at the batch.cpp:244 seam, on its resident
+        copy (slam_undistort_batch): a ResidentFrame whose host pixels (the point
+        colours are read from them) and HBM copy are the undistorted ones.
+        Frames the device batch path does not take (not BGR) go through the
+        host-buffer entry point."""
+        from .api import undistort, undistortBatch
+        frame = self.ingest(frame)
+        dev = getattr(frame, "dev", None)
+        if dev is None:
+            return undistort(frame, K, dist, newK, ctx=self.ctx)
+        out = undistortBatch(dev.unsqueeze(0), K, dist, newK, ctx=self.ctx)[0]
+        r = out.cpu().numpy().view(ResidentFrame)     # the copy waits for the launch
+        r.dev = out
+        return r
+
     def _batches(self):
         if self._db is None:
             from .batch import DeviceBatch
@@ -483,6 +499,39 @@ class DeviceMedia:
                 break
             out.append(f)
         return out
+
+
+class UndistortedMedia:
+    """Any media with cv::undistort(frame, K, dist, newK) applied where the
+    reference marks the seam (batch.cpp:244, between getNextFrame and
+    fastExtractor): next_frame() is ops.undistort of the inner media's frame.
+    Over a DeviceMedia the whole resident sequence is undistorted in one
+    slam_undistort_batch and the frames handed out are views of the result, so a
+    batch's frames stay one contiguous range and take(n) keeps working (the
+    attribute exists only then: fillVideoFrameBatch tests for it)."""
+
+    def __init__(self, media, K, dist, ops, newK=None):
+        self.media, self.ops = media, ops
+        self.K = np.array(K, np.float64)     # a copy: BA refines the pipeline's K in place
+        self.dist = np.array(dist, np.float64).reshape(-1)
+        self.newK = None if newK is None else np.array(newK, np.float64)
+        self._seq = None
+        if isinstance(media, DeviceMedia):
+            from .api import undistortBatch
+            rest = media.dev[media.i:]
+            dev = undistortBatch(rest, self.K, self.dist, self.newK, ctx=ops.ctx)
+            host = dev.cpu().numpy() if media.host is not None else None
+            media.i = len(media.dev)         # the inner sequence is consumed
+            self._seq = DeviceMedia(host, dev)
+            self.take = self._seq.take
+
+    def next_frame(self):
+        if self._seq is not None:
+            return self._seq.next_frame()
+        f = self.media.next_frame()
+        if f is None:
+            return None
+        return self.ops.undistort(f, self.K, self.dist, self.newK)
 
 
 class MediaSources:
@@ -1058,12 +1107,17 @@ def define_camera_position(old_deque, last_id, fd):
         fd.motion = old_deque[last_id].motion.copy()
 
 
-def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None):
+def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK=None):
     """src/main.cpp:71-107 slamMain: mainCycle restarts from the last pose until
     the sequence ends, then points.txt / colors.txt.  K (3x3 float64) is
-    updated in place by BA, as the reference's calibrationMatrix is.  Returns
-    (GlobalData, Logs)."""
+    updated in place by BA, as the reference's calibrationMatrix is.  dist: the
+    calibration file's distortion coefficients (load_calibration(path, "DC"));
+    when given and not all zero every frame is undistorted as it leaves the
+    media (UndistortedMedia, the batch.cpp:244 seam; newK as cv::undistort's),
+    otherwise nothing changes.  Returns (GlobalData, Logs)."""
     ops = ops or GpuOps()
+    if dist is not None and np.any(np.asarray(dist, np.float64) != 0):
+        media = UndistortedMedia(media, K, dist, ops, newK)
     cond = Conditions(cfg)
     logs = Logs(out_dir if out_dir is not None else None)
     gd = GlobalData()
