@@ -510,6 +510,38 @@ int slam_undistort(slam_ctx* ctx, const uint8_t* img, int w, int h, size_t step,
 int slam_undistort_map(slam_ctx* ctx, int w, int h, const double* K, const double* dist, int ndist,
                        const double* newK, int16_t* xy, uint16_t* frac);
 
+/* cv::undistortPoints(src, dst, K, D, noArray(), P, criteria) (OpenCV 4.8,
+ * cvUndistortPointsInternal for CV_32FC2 points, uncontracted f64, no tilt): the
+ * seams the reference marks at batch.cpp:244 and mainCycleInternals.cpp:142 ("In
+ * future we can do UNDISTORTION here") taken for the keypoints that reach
+ * geometry instead of the frames.  n points (x, y as floats) are read at src + i *
+ * src_stride bytes (src_stride >= 8 and a multiple of 4; 28 reads slam_keypoint.pt
+ * in place) and written packed to dst (n x 2); dst == src with stride 8 is
+ * allowed, any other overlap is refused.  K and dist as above (only fx, fy, cx,
+ * cy of K are used: a skew entry is ignored, as OpenCV ignores it); P: 3x3
+ * row-major applied to the normalised result, or NULL for normalised
+ * coordinates.  Criteria: max_iter in 1..1000; eps == 0 iterates max_iter times
+ * (OpenCV's default is 5, 0), eps > 0 also stops once the reprojection error
+ * is below eps pixels.  A criterion without a count is not offered: OpenCV's
+ * loops forever on a point that never converges.  OpenCV's exit on a negative
+ * inverse radial factor (the point goes back to its start value) is kept.
+ * err (n floats, or NULL): the distance in pixels between the input point and
+ * the forward model of the returned one, which OpenCV does not report; a point
+ * beyond the fold of the radial polynomial has no preimage and keeps a large
+ * residual, so callers test err <= tol (a NaN fails it).
+ * SLAM_E_UNSUPPORTED for ndist 14; SLAM_E_INVALID_ARG for any other bad count,
+ * null pointers with n > 0, n < 0, bad criteria, a bad stride or a device
+ * pointer that is not 4-byte aligned; n == 0 succeeds without a launch.
+ *
+ * slam_undistort_points: host memory in and out, synchronous. */
+int slam_undistort_points(slam_ctx* ctx, const float* src, size_t src_stride, int n, const double* K,
+                          const double* dist, int ndist, const double* P, int max_iter, double eps, float* dst,
+                          float* err);
+/* the same on device memory on `stream` (NULL = the context stream), no host sync */
+int slam_undistort_points_dev(slam_ctx* ctx, void* stream, const float* d_src, size_t src_stride, int n,
+                              const double* K, const double* dist, int ndist, const double* P, int max_iter,
+                              double eps, float* d_dst, float* d_err);
+
 /* ---- options ------------------------------------------------------------------ */
 /* Per-context choices; all but SLAM_OPT_PNP_SUMS (below) never change results.  SLAM_OPT_SIFT_KERNEL picks the
  * kernel for SIFT descriptors of keypoints sharing one angle and size (FAST

@@ -419,7 +419,7 @@ void slam_destroy(slam_ctx* c)
                       &c->match_cnt, &c->match_out, &c->frames_in, &c->qbuf, &c->tbuf, &c->misc, &c->ba_obs,
                       &c->ba_par, &c->ba_jac, &c->ba_red, &c->ba_S, &c->ba_aux, &c->sd_pyr, &c->sd_cand,
                       &c->sd_kps, &c->sd_kpc, &c->sift_tab, &c->sift_band_buf, &c->sift_cols_buf, &c->sift_cols_park, &c->sift_colw_buf, &c->sift_split, &c->sift_split_cnt, &c->sift_deal, &c->geom, &c->cluster, &c->delaunay,
-                      &c->undist_xy, &c->undist_frac, &c->undist_out};
+                      &c->undist_xy, &c->undist_frac, &c->undist_out, &c->undist_pts};
     for (DevBuf* b : bufs) b->release();
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->ev_up) (void)hipEventDestroy(c->ev_up);
@@ -1247,6 +1247,66 @@ int slam_undistort_map(slam_ctx* c, int w, int h, const double* K, const double*
     SLAM_HIP(c, hipMemcpyAsync(xy, c->undist_xy.p, n * 2 * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
     SLAM_HIP(c, hipMemcpyAsync(frac, c->undist_frac.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
     if (int rc = undist_mark(c, c->stream)) return rc;
+    return stream_sync(c, c->stream);
+}
+
+// ---- cv::undistortPoints for the keypoints that reach geometry (undistort.hip) ----
+
+static int undist_points_args(slam_ctx* c, const float* src, size_t src_stride, int n, const float* dst)
+{
+    if (n < 0) return set_err(c, SLAM_E_INVALID_ARG, "undistort points: negative point count");
+    if (src_stride < 8 || src_stride % 4 != 0)
+        return set_err(c, SLAM_E_INVALID_ARG, "undistort points: the stride is at least 8 bytes and a multiple of 4");
+    if (n > 0 && (!src || !dst)) return set_err(c, SLAM_E_INVALID_ARG, "undistort points: null points");
+    return SLAM_OK;
+}
+
+int slam_undistort_points_dev(slam_ctx* c, void* stream, const float* d_src, size_t src_stride, int n, const double* K,
+                              const double* dist, int ndist, const double* P, int max_iter, double eps, float* d_dst,
+                              float* d_err)
+{
+    if (!c) return SLAM_E_INVALID_ARG;
+    if (int rc = undist_points_args(c, d_src, src_stride, n, d_dst)) return rc;
+    UndistPointsParams prm;
+    if (int rc = undist_points_params(c, K, dist, ndist, P, max_iter, eps, &prm)) return rc;
+    if (n == 0) return SLAM_OK;   // nothing to do: no launch
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_src), b = reinterpret_cast<uintptr_t>(d_dst),
+                    e = reinterpret_cast<uintptr_t>(d_err);
+    if ((a | b | e) & 3u) return set_err(c, SLAM_E_INVALID_ARG, "undistort points: device pointers are 4-byte aligned");
+    // a thread reads its point before it writes, so the result may replace packed
+    // points exactly; any other overlap would let one thread write what another reads
+    const size_t sa = (size_t)(n - 1) * src_stride + 8, sb = (size_t)n * 8, se = (size_t)n * 4;
+    const bool in_place = a == b && src_stride == 8;
+    if ((!in_place && a < b + sb && b < a + sa) || (e && ((a < e + se && e < a + sa) || (b < e + se && e < b + sb))))
+        return set_err(c, SLAM_E_INVALID_ARG, "undistort points: points, results and residuals overlap");
+    SLAM_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    SLAM_HIP(c, launch_undist_points(s, prm, d_src, src_stride, n, d_dst, d_err));
+    return SLAM_OK;
+}
+
+int slam_undistort_points(slam_ctx* c, const float* src, size_t src_stride, int n, const double* K, const double* dist,
+                          int ndist, const double* P, int max_iter, double eps, float* dst, float* err)
+{
+    if (!c) return SLAM_E_INVALID_ARG;
+    if (int rc = async_guard(c)) return rc;
+    if (int rc = undist_points_args(c, src, src_stride, n, dst)) return rc;
+    UndistPointsParams prm;
+    if (int rc = undist_points_params(c, K, dist, ndist, P, max_iter, eps, &prm)) return rc;
+    if (n == 0) return SLAM_OK;
+    SLAM_HIP(c, hipSetDevice(c->device));
+    // device layout: the points at the caller's stride, then n x 2 results, then n residuals
+    const size_t sa = ((size_t)(n - 1) * src_stride + 8 + 15) & ~(size_t)15, sb = (size_t)n * 8, se = (size_t)n * 4;
+    SLAM_HIP(c, c->undist_pts.ensure(sa + sb + se));
+    char* base = c->undist_pts.as<char>();
+    float* d_src = reinterpret_cast<float*>(base);
+    float* d_dst = reinterpret_cast<float*>(base + sa);
+    float* d_err = reinterpret_cast<float*>(base + sa + sb);
+    SLAM_HIP(c, hipMemcpyAsync(d_src, src, (size_t)(n - 1) * src_stride + 8, hipMemcpyHostToDevice, c->stream));
+    SLAM_HIP(c, launch_undist_points(c->stream, prm, d_src, src_stride, n, d_dst, err ? d_err : nullptr));
+    // dst may be src (stride 8): the upload above is complete before this copy lands
+    SLAM_HIP(c, hipMemcpyAsync(dst, d_dst, sb, hipMemcpyDeviceToHost, c->stream));
+    if (err) SLAM_HIP(c, hipMemcpyAsync(err, d_err, se, hipMemcpyDeviceToHost, c->stream));
     return stream_sync(c, c->stream);
 }
 

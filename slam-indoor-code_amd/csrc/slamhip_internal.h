@@ -276,6 +276,7 @@ struct slam_ctx {
     // undistortion map of one (K, newK, D, w, h) (undistort.hip): CV_16SC2 + CV_16UC1
     slamhip::DevBuf undist_xy, undist_frac;
     slamhip::DevBuf undist_out;           // slam_undistort: the device result of a host frame
+    slamhip::DevBuf undist_pts;           // slam_undistort_points: the host points and their results
     bool undist_valid = false;
     double undist_key[30] = {};           // K, newK (K when absent), the 12 coefficients
     int undist_w = 0, undist_h = 0;
@@ -460,6 +461,21 @@ int undist_mark(slam_ctx* c, hipStream_t s);
 // remap of nframes packed frames (n x h x w x channels, channels 1 or 3) through the cached map
 hipError_t launch_undist_remap(slam_ctx* c, hipStream_t s, const uint8_t* src, uint8_t* dst, int nframes, int w, int h,
                                int channels);
+// undist_points: the camera, the 12 coefficients, RR (P, or the identity) and the criteria as kernel arguments
+constexpr int kUndistMaxIter = 1000;
+struct UndistPointsParams {
+    double fx, fy, cx, cy, ifx, ify;
+    double k[12];   // k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4
+    double RR[9];
+    double eps;
+    int max_iter, use_eps;
+};
+// validates the model and the criteria (max_iter 1..kUndistMaxIter, eps >= 0; eps == 0: count only)
+int undist_points_params(slam_ctx* c, const double* K, const double* dist, int ndist, const double* P, int max_iter,
+                         double eps, UndistPointsParams* out);
+// n > 0 points read at src + i * src_stride; dst n x 2 packed, err n or null; dst == src allowed at stride 8
+hipError_t launch_undist_points(hipStream_t s, const UndistPointsParams& P, const float* src, size_t src_stride, int n,
+                                float* dst, float* err);
 
 // ---- BA (ba.hip) ----
 int ba_solve(slam_ctx* c, double* K4, int nframes, double* ext6, int npoints, double* pts3, int nobs,

@@ -12,8 +12,18 @@
 //                 integer arithmetic.  A workgroup owns one destination tile and
 //                 loops over a chunk of frames with the map entries and weights
 //                 unpacked once; a thread produces 4 consecutive pixels.
+//
+// and cv::undistortPoints for the keypoints that reach geometry (the same seam,
+// and the one findFirstGoodFrame marks at mainCycleInternals.cpp:142, taken the
+// cheap way):
+//
+//   undist_points cvUndistortPointsInternal for CV_32FC2 points without R: the
+//                 fixed-point iteration of the inverse model, one thread per
+//                 point in uncontracted f64, with the reprojection residual of
+//                 the returned point as a second output.
 #include "slamhip_internal.h"
 
+#include <cfloat>
 #include <climits>
 #include <cstring>
 
@@ -216,6 +226,70 @@ __global__ __launch_bounds__(kRemapThreads) void undist_remap(const uint8_t* __r
     }
 }
 
+// ---- undistortPoints -------------------------------------------------------------
+
+// the forward model at (x, y) and its pixel distance to the input point (u, v):
+// the EPS block of cvUndistortPointsInternal, operation by operation
+__device__ __forceinline__ double undist_reproject(const UndistPointsParams& P, double x, double y, double u, double v)
+{
+    const double* k = P.k;
+    const double r2 = x * x + y * y;
+    const double r4 = r2 * r2;
+    const double r6 = r4 * r2;
+    const double a1 = 2 * x * y;
+    const double a2 = r2 + 2 * x * x;
+    const double a3 = r2 + 2 * y * y;
+    const double cdist = 1 + k[0] * r2 + k[1] * r4 + k[4] * r6;
+    const double icdist2 = 1. / (1 + k[5] * r2 + k[6] * r4 + k[7] * r6);
+    const double xd = x * cdist * icdist2 + k[2] * a1 + k[3] * a2 + k[8] * r2 + k[9] * r4;
+    const double yd = y * cdist * icdist2 + k[2] * a3 + k[3] * a1 + k[10] * r2 + k[11] * r4;
+    const double dx = xd * P.fx + P.cx - u;
+    const double dy = yd * P.fy + P.cy - v;
+    return sqrt(dx * dx + dy * dy);
+}
+
+constexpr int kPointThreads = 256;
+
+// One thread per point.  The lanes of a wave leave the loop at different j;
+// max_iter (at most kUndistMaxIter) bounds the launch.  A point is read before
+// its result is written, so dst may be src itself (stride 8).
+__global__ __launch_bounds__(kPointThreads) void undist_points(UndistPointsParams P, const float* src, size_t src_stride,
+                                                               int n, float* dst, float* err)
+{
+    const int i = blockIdx.x * kPointThreads + threadIdx.x;
+    if (i >= n) return;
+    const float* s = reinterpret_cast<const float*>(reinterpret_cast<const char*>(src) + (size_t)i * src_stride);
+    const double u = s[0], v = s[1];
+    const double* k = P.k;
+    double x = (u - P.cx) * P.ifx, y = (v - P.cy) * P.ify;
+    const double x0 = x, y0 = y;
+    double error = DBL_MAX;
+    for (int j = 0;; j++) {
+        if (j >= P.max_iter) break;
+        if (P.use_eps && error < P.eps) break;
+        const double r2 = x * x + y * y;
+        const double icdist = (1 + ((k[7] * r2 + k[6]) * r2 + k[5]) * r2) / (1 + ((k[4] * r2 + k[1]) * r2 + k[0]) * r2);
+        if (icdist < 0) {   // OpenCV's test of regression 14583: back to the start value (kept)
+            x = (u - P.cx) * P.ifx;
+            y = (v - P.cy) * P.ify;
+            break;
+        }
+        const double deltaX = 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x) + k[8] * r2 + k[9] * r2 * r2;
+        const double deltaY = k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y + k[10] * r2 + k[11] * r2 * r2;
+        x = (x0 - deltaX) * icdist;
+        y = (y0 - deltaY) * icdist;
+        if (P.use_eps) error = undist_reproject(P, x, y, u, v);
+    }
+    // the residual of the point that is returned (ours: OpenCV does not report it)
+    if (err) err[i] = (float)undist_reproject(P, x, y, u, v);
+    const double* RR = P.RR;
+    const double xx = RR[0] * x + RR[1] * y + RR[2];
+    const double yy = RR[3] * x + RR[4] * y + RR[5];
+    const double ww = 1. / (RR[6] * x + RR[7] * y + RR[8]);
+    dst[2 * (size_t)i] = (float)(xx * ww);
+    dst[2 * (size_t)i + 1] = (float)(yy * ww);
+}
+
 hipError_t build_map(slam_ctx* c, hipStream_t s, const UndistParams& P)
 {
     hipLaunchKernelGGL(undist_map, dim3((P.h + kMapThreads - 1) / kMapThreads), dim3(kMapThreads), 0, s, P,
@@ -292,6 +366,43 @@ hipError_t launch_undist_remap(slam_ctx* c, hipStream_t s, const uint8_t* src, u
         hipLaunchKernelGGL(undist_remap<1>, grid, dim3(kRemapThreads), 0, s, src, dst, xy, fr, nframes, w, h);
     else
         hipLaunchKernelGGL(undist_remap<3>, grid, dim3(kRemapThreads), 0, s, src, dst, xy, fr, nframes, w, h);
+    return hipGetLastError();
+}
+
+int undist_points_params(slam_ctx* c, const double* K, const double* dist, int ndist, const double* P, int max_iter,
+                         double eps, UndistPointsParams* out)
+{
+    if (!K || (ndist > 0 && !dist))
+        return set_err(c, SLAM_E_INVALID_ARG, "undistort points: null camera matrix or coefficients");
+    if (ndist == 14)
+        return set_err(c, SLAM_E_UNSUPPORTED, "undistort points: the 14-coefficient tilt model is not supported");
+    if (ndist != 4 && ndist != 5 && ndist != 8 && ndist != 12)
+        return set_err(c, SLAM_E_INVALID_ARG, "undistort points: 4, 5, 8 or 12 distortion coefficients");
+    // a count is required: OpenCV's EPS-only loop never ends on a point that does not converge
+    if (max_iter < 1 || max_iter > kUndistMaxIter || !(eps >= 0) || eps > DBL_MAX)
+        return set_err(c, SLAM_E_INVALID_ARG, "undistort points: criteria are 1..1000 iterations and a finite eps >= 0");
+    std::memset(out, 0, sizeof(*out));
+    out->fx = K[0];
+    out->fy = K[4];
+    out->cx = K[2];
+    out->cy = K[5];
+    out->ifx = 1. / K[0];
+    out->ify = 1. / K[4];
+    std::memcpy(out->k, dist, sizeof(double) * ndist);
+    if (P) std::memcpy(out->RR, P, sizeof(out->RR));
+    else out->RR[0] = out->RR[4] = out->RR[8] = 1.;
+    out->max_iter = max_iter;
+    out->use_eps = eps > 0;
+    out->eps = eps;
+    return SLAM_OK;
+}
+
+hipError_t launch_undist_points(hipStream_t s, const UndistPointsParams& P, const float* src, size_t src_stride, int n,
+                                float* dst, float* err)
+{
+    hipLaunchKernelGGL(undist_points, dim3((unsigned)(((size_t)n + kPointThreads - 1) / kPointThreads)), dim3(kPointThreads), 0, s,
+                       P, src,
+                       src_stride, n, dst, err);
     return hipGetLastError();
 }
 

@@ -20,7 +20,7 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
                   SYNTH_DRIFT, SYNTH_STEADY, synth_frames_dev,
                   clusterizePoints, clusterLabels, getBestFittingPlaneByPoints, planeMoments, projectToPlane,
                   delaunay2d, delaunay2dHost, delaunayStats, delaunayPredicates, meshFilter,
-                  load_calibration, undistort, undistortBatch, undistortMap)
+                  load_calibration, undistort, undistortBatch, undistortMap, undistortPoints)
 from .config import ConfigError, ConfigService, reference_example
 
 __all__ = [n for n in dir() if not n.startswith("_")]

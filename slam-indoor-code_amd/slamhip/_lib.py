@@ -126,6 +126,8 @@ SIGNATURES = {
     "slam_undistort_batch": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
     "slam_undistort": (_I, [_P, _P, _I, _I, _SZ, _I, _P, _P, _I, _P, _P, _SZ]),
     "slam_undistort_map": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "slam_undistort_points": (_I, [_P, _P, _SZ, _I, _P, _P, _I, _P, _I, _D, _P, _P]),
+    "slam_undistort_points_dev": (_I, [_P, _P, _P, _SZ, _I, _P, _P, _I, _P, _I, _D, _P, _P]),
 }
 
 _lib = None

@@ -745,6 +745,37 @@ def undistortBatch(frames, K, dist, newK=None, ctx=None, out=None, stream=None):
     return out
 
 
+def undistortPoints(pts_or_keypoints, K, dist, P=None, criteria=(5, 0.0), ctx=None):
+    """cv::undistortPoints(src, dst, K, dist, noArray(), P, criteria)
+    (slam_undistort_points): the ideal position of distorted image points, for
+    the keypoints that reach geometry when the frames stay raw (the
+    batch.cpp:244 seam without the frame remap).  pts_or_keypoints: n x 2
+    float32 points, or a keypoint record array, whose .pt is read in place.
+    P: 3x3 applied to the normalised result (None: normalised coordinates).
+    criteria = (max_iter, eps): max_iter in 1..1000; eps == 0 iterates max_iter
+    times (OpenCV's default: 5), eps > 0 also stops below eps pixels of
+    reprojection error.  Returns (xy float32 n x 2, err float32 n); err is the
+    distance in pixels between each input point and the distortion model of its
+    result.  A point beyond the fold of the lens model has no preimage: test
+    err <= tol before using xy (a NaN fails the test)."""
+    c = _ctx(ctx)
+    a = np.asarray(pts_or_keypoints)
+    if a.dtype == KEYPOINT_DTYPE:
+        a = np.ascontiguousarray(a).reshape(-1)
+        stride = KEYPOINT_DTYPE.itemsize
+    else:
+        a = np.ascontiguousarray(a, np.float32).reshape(-1, 2)
+        stride = 8
+    K, d, p = _camera(K, dist, P)
+    max_iter, eps = criteria
+    n = len(a)
+    xy = np.empty((n, 2), np.float32)
+    err = np.empty(n, np.float32)
+    check(lib().slam_undistort_points(c, ptr(a), stride, n, ptr(K), ptr(d), d.size, ptr(p), int(max_iter), float(eps),
+                                      ptr(xy), ptr(err)), c)
+    return xy, err
+
+
 SYNTH_DRIFT, SYNTH_STEADY = 0, 1
 
 

@@ -164,6 +164,14 @@ class GpuOps:
         r.dev = out
         return r
 
+    def undistort_points(self, kps, K, dist, P=None, criteria=(5, 0.0)):
+        """cv::undistortPoints of a keypoint record array, its .pt read in place
+        at the record stride (slam_undistort_points): (xy float32 n x 2, err
+        float32 n).  Runs on the search context: call it from the thread that
+        runs the searches."""
+        from .api import undistortPoints
+        return undistortPoints(np.ascontiguousarray(kps, KEYPOINT_DTYPE), K, dist, P, criteria, ctx=self.ctx)
+
     def _batches(self):
         if self._db is None:
             from .batch import DeviceBatch
@@ -556,20 +564,79 @@ class MediaSources:
         return None
 
 
-class TemporalImageData:
-    """mainCycleStructures.h:38-45."""
+class PointLens:
+    """slam_main(undistort="points"): the lens model the keypoints that reach
+    geometry are undistorted with (cv::undistortPoints through
+    ops.undistort_points) instead of the frames.  lens(kps) is (xy float32
+    n x 2 in the pixels of P, valid bool n); a keypoint whose residual exceeds
+    max_residual pixels (or is NaN) has no undistorted position: it lies beyond
+    the fold of the lens model, or the iteration did not reach it."""
 
-    def __init__(self):
-        self.allExtractedFeatures = np.zeros(0, KEYPOINT_DTYPE)
+    def __init__(self, ops, K, dist, P, criteria, max_residual):
+        self.ops = ops
+        self.K = np.array(K, np.float64)       # copies: BA refines the pipeline's K in place
+        self.dist = np.array(dist, np.float64).reshape(-1)
+        self.P = np.array(P, np.float64)
+        self.criteria = (int(criteria[0]), float(criteria[1]))
+        self.max_residual = float(max_residual)
+
+    def __call__(self, kps):
+        xy, err = self.ops.undistort_points(kps, self.K, self.dist, self.P, self.criteria)
+        return xy, err <= np.float32(self.max_residual)
+
+
+def drop_invalid_matches(prev, nxt, matches):
+    """undistort="points": a match with an endpoint that has no undistorted
+    position leaves the list before anything reads it"""
+    if nxt.lens is None or len(matches) == 0:
+        return matches
+    keep = prev.valid[matches["queryIdx"]] & nxt.valid[matches["trainIdx"]]
+    return matches if keep.all() else matches[keep]
+
+
+class TemporalImageData:
+    """mainCycleStructures.h:38-45.  With a lens (PointLens) the holder also
+    carries its keypoints' undistorted coordinates and their validity mask,
+    computed when the features are set and again whenever they are replaced."""
+
+    def __init__(self, lens=None):
+        self.lens = lens
+        # (features, undistorted xy, valid) replaced as one object: the post-search
+        # worker may read a holder while the search thread replaces its features
+        self._f = (np.zeros(0, KEYPOINT_DTYPE), None, None)
+        if lens is not None:
+            self._f = (self._f[0], np.zeros((0, 2), np.float32), np.zeros(0, bool))
         self.allMatches = np.zeros(0, DMATCH_DTYPE)
         self.rotation = None
         self.motion = None
         self.correspondSpatialPointIdx = np.zeros(0, np.int64)
 
+    @property
+    def allExtractedFeatures(self):
+        return self._f[0]
+
+    @allExtractedFeatures.setter
+    def allExtractedFeatures(self, v):
+        if self.lens is None:
+            self._f = (v, None, None)
+        else:
+            xy, valid = self.lens(v)
+            self._f = (v, xy, valid)
+
+    @property
+    def undistorted(self):
+        """the keypoints' undistorted coordinates (n x 2 float32), None without a lens"""
+        return self._f[1]
+
+    @property
+    def valid(self):
+        return self._f[2]
+
     def snapshot(self):
         """std::vector push_back copy: vectors deep, cv::Mat shallow."""
-        s = TemporalImageData()
-        s.allExtractedFeatures = self.allExtractedFeatures.copy()
+        s = TemporalImageData(self.lens)
+        f, xy, valid = self._f
+        s._f = (f.copy(), xy, valid)         # the undistorted arrays are never written: shared
         s.allMatches = self.allMatches.copy()
         s.rotation = self.rotation
         s.motion = self.motion
@@ -681,7 +748,10 @@ class Logs:
                     raw_output(gd.spatialPointsColors, f)
 
 
-def _pts(kps, idx):
+def _pts(kps, idx, xy=None):
+    """the coordinates of keypoints idx; xy: their undistorted coordinates, read instead of the raw ones"""
+    if xy is not None:
+        return np.ascontiguousarray(xy[idx], np.float32).reshape(-1, 2)
     return np.stack([kps["x"][idx], kps["y"][idx]], 1).astype(np.float32) if len(idx) else np.zeros((0, 2), np.float32)
 
 
@@ -812,13 +882,14 @@ def find_first_good_frame(media, cond, holder, ops):
             return frame
 
 
-def key_point_coords(f1, f2, matches):
+def key_point_coords(f1, f2, matches, xy1=None, xy2=None):
     """getKeyPointCoordsFromFramePair: (queryIdx pts of frame 1, trainIdx pts of frame 2)."""
-    return _pts(f1, matches["queryIdx"]), _pts(f2, matches["trainIdx"])
+    return _pts(f1, matches["queryIdx"], xy1), _pts(f2, matches["trainIdx"], xy2)
 
 
 def compute_transformation_and_filter_points(cond, K, d0, d1, ops):
-    p1, p2 = key_point_coords(d0.allExtractedFeatures, d1.allExtractedFeatures, d1.allMatches)
+    p1, p2 = key_point_coords(d0.allExtractedFeatures, d1.allExtractedFeatures, d1.allMatches, d0.undistorted,
+                              d1.undistorted)
     ok, R, t, chir = ops.estimate_transformation(p1, p2, K, cond.rpUseRansac, cond.rpProb, cond.rpThreshold,
                                                  cond.rpDistance)
     if R is None:
@@ -845,11 +916,11 @@ def define_features_correspond_spatial_indices(mask, second_frame, d0, d1):
     return _colors(second_frame, d1.allExtractedFeatures[m["trainIdx"]])
 
 
-def old_spatial_points_and_new_coords(matches, prev_idx, points, new_kps):
+def old_spatial_points_and_new_coords(matches, prev_idx, points, new_kps, new_xy=None):
     sel = prev_idx[matches["queryIdx"]] if len(matches) else np.zeros(0, np.int64)
     keep = sel >= 0
     obj = points[sel[keep]].astype(np.float32) if keep.any() else np.zeros((0, 3), np.float32)
-    img = _pts(new_kps, matches["trainIdx"][keep]) if keep.any() else np.zeros((0, 2), np.float32)
+    img = _pts(new_kps, matches["trainIdx"][keep], new_xy) if keep.any() else np.zeros((0, 2), np.float32)
     return obj, img
 
 
@@ -914,11 +985,11 @@ def start_bundle_adjustment(K, window, gd, cond, ops, stats=None):
     for i, im in enumerate(window):
         ext[i, :3] = rodrigues_to_vector(im.rotation)
         ext[i, 3:] = im.motion.reshape(3)
-        kps = im.allExtractedFeatures
+        kps, uxy = im.allExtractedFeatures, im.undistorted
         p = np.nonzero(im.correspondSpatialPointIdx >= 0)[0]
         of.append(np.full(len(p), i, np.int32))
         op.append(im.correspondSpatialPointIdx[p].astype(np.int32))
-        oxy.append(np.stack([kps["x"][p], kps["y"][p]], 1).astype(np.float64))
+        oxy.append((np.stack([kps["x"][p], kps["y"][p]], 1) if uxy is None else uxy[p]).astype(np.float64))
     pts = np.ascontiguousarray(gd.spatialPoints, np.float64).copy()
     of, op, oxy = np.concatenate(of), np.concatenate(op), np.concatenate(oxy).reshape(-1, 2)
     inputs = None
@@ -955,7 +1026,8 @@ def define_first_pair_frames(cond, media, batch, deque, ops):
         if idx == EMPTY_BATCH:
             return EMPTY_BATCH, None
         if idx >= 0:
-            deque[1].allExtractedFeatures, deque[1].allMatches = feats, matches
+            deque[1].allExtractedFeatures = feats
+            deque[1].allMatches = drop_invalid_matches(deque[0], deque[1], matches)
             return idx, frame
         first = batch[0].frame
         deque[0].allExtractedFeatures = batch[0].features.copy()
@@ -1006,13 +1078,14 @@ def main_cycle(media, K, cond, deque, gd, logs, ops, stats=None):
         if pending is not None:
             pending.finish()            # K / R / t / points before PnP reads them
         obj, img = old_spatial_points_and_new_coords(nxt.allMatches, prev.correspondSpatialPointIdx,
-                                                     gd.spatialPoints, nxt.allExtractedFeatures)
+                                                     gd.spatialPoints, nxt.allExtractedFeatures, nxt.undistorted)
         found, rvec, tvec = ops.solve_pnp(obj, img, K)
         nxt.motion = np.asarray(tvec, np.float64).reshape(3, 1).copy()
         nxt.rotation = ops.rodrigues(rvec)
         logs.pose(nxt.rotation, nxt.motion)
 
-        p1, p2 = key_point_coords(prev.allExtractedFeatures, nxt.allExtractedFeatures, nxt.allMatches)
+        p1, p2 = key_point_coords(prev.allExtractedFeatures, nxt.allExtractedFeatures, nxt.allMatches,
+                                  prev.undistorted, nxt.undistorted)
         new_points = ops.reconstruct(K, prev.rotation, prev.motion, nxt.rotation, nxt.motion, p1, p2)
         push_new_spatial_points(frame, new_points, gd, prev.correspondSpatialPointIdx, nxt)
 
@@ -1057,7 +1130,8 @@ def main_cycle(media, K, cond, deque, gd, logs, ops, stats=None):
             bidx, frame, feats, matches = find_good_frame_from_batch(media, cond, batch, last_good, prev, ops)
             if bidx == EMPTY_BATCH or bidx == FRAME_NOT_FOUND:
                 break
-            nxt.allExtractedFeatures, nxt.allMatches = feats, matches
+            nxt.allExtractedFeatures = feats
+            nxt.allMatches = matches = drop_invalid_matches(prev, nxt, matches)
             if worker is not None:
                 decided, verdict = threading.Event(), {}
                 fut = worker.submit(checked_post, prev, nxt, frame, decided, verdict)
@@ -1074,7 +1148,7 @@ def main_cycle(media, K, cond, deque, gd, logs, ops, stats=None):
             last_good = frame
             if last == OPTIMAL_DEQUE_SIZE - 2:
                 deque.pop(0)
-                deque.append(TemporalImageData())
+                deque.append(TemporalImageData(deque[0].lens))
             else:
                 last += 1
             if stats is not None:
@@ -1107,17 +1181,35 @@ def define_camera_position(old_deque, last_id, fd):
         fd.motion = old_deque[last_id].motion.copy()
 
 
-def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK=None):
+def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK=None, undistort="frames",
+              criteria=(50, 0.01), max_residual=0.01):
     """src/main.cpp:71-107 slamMain: mainCycle restarts from the last pose until
     the sequence ends, then points.txt / colors.txt.  K (3x3 float64) is
     updated in place by BA, as the reference's calibrationMatrix is.  dist: the
     calibration file's distortion coefficients (load_calibration(path, "DC"));
     when given and not all zero every frame is undistorted as it leaves the
     media (UndistortedMedia, the batch.cpp:244 seam; newK as cv::undistort's),
-    otherwise nothing changes.  Returns (GlobalData, Logs)."""
+    otherwise nothing changes.
+
+    undistort="points" takes the seam the cheap way: the frames stay raw (FAST,
+    the descriptors, the candidate search and its match counts are those of a
+    run without coefficients) and only the keypoints that reach geometry are
+    undistorted, by cv::undistortPoints with K as it is at entry, P = newK (K
+    when absent) and `criteria` = (max iterations, eps in pixels).  A keypoint
+    whose residual exceeds max_residual pixels has no undistorted position; a
+    winner's matches that touch one are dropped before anything reads them.  The
+    essential matrix, PnP, triangulation and BA read the undistorted
+    coordinates; the point colours are read from the raw frame at the raw
+    coordinates, the same physical pixel.  Returns (GlobalData, Logs)."""
+    if undistort not in ("frames", "points"):
+        raise ValueError('undistort: "frames" or "points"')
     ops = ops or GpuOps()
+    lens = None
     if dist is not None and np.any(np.asarray(dist, np.float64) != 0):
-        media = UndistortedMedia(media, K, dist, ops, newK)
+        if undistort == "frames":
+            media = UndistortedMedia(media, K, dist, ops, newK)
+        else:
+            lens = PointLens(ops, K, dist, K if newK is None else newK, criteria, max_residual)
     cond = Conditions(cfg)
     logs = Logs(out_dir if out_dir is not None else None)
     gd = GlobalData()
@@ -1129,7 +1221,7 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
         media = prefetch(media, cond.featureExtractingThreshold)
     try:
         while True:
-            deque = [TemporalImageData() for _ in range(OPTIMAL_DEQUE_SIZE)]
+            deque = [TemporalImageData(lens) for _ in range(OPTIMAL_DEQUE_SIZE)]
             define_camera_position(old, last_id, deque[0])
             ngd = GlobalData()
             last_id = main_cycle(media, K, cond, deque, ngd, logs, ops, stats)
