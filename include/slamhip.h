@@ -542,6 +542,63 @@ int slam_undistort_points_dev(slam_ctx* ctx, void* stream, const float* d_src, s
                               const double* K, const double* dist, int ndist, const double* P, int max_iter,
                               double eps, float* d_dst, float* d_err);
 
+/* ---- chessboard calibration ------------------------------------------------------ */
+/* The reference's "calibrate" mode (cameraCalibration.cpp:142-203):
+ * findChessboardCorners -> cornerSubPix -> calibrateCamera.  The detector is this
+ * library's own (tests/calib_ref.py defines it); cornerSubPix
+ * restates OpenCV 4.8; calibrateCamera returns the optimum of OpenCV's model.
+ *
+ * slam_chess_candidates: corner candidates of one frame in host memory (8-bit,
+ * channels 1 or 3 = BGR).  The level image is the s x s area mean of the gray
+ * frame, s = max(1, ceil(max(w, h) / 1024)) (returned in *scale); out holds
+ * *n_out rows (x, y, R) of int32 in level coordinates, raster order.  A level of
+ * W x H pixels has at most ceil(W / 8) * ceil(H / 8) candidates; SLAM_E_CAPACITY
+ * if more than cap were found (*n_out = the needed number, nothing written). */
+int slam_chess_candidates(slam_ctx* ctx, const uint8_t* img, int w, int h, size_t step, int channels, int32_t* out,
+                          int cap, int* n_out, int* scale);
+/* the same for nframes packed frames resident in HBM (n x h x w x channels), one
+ * launch per kernel for the batch, on `stream` (NULL = the context stream).
+ * out (host): nframes x cap x 3; n_out (host): nframes counts; synchronous. */
+int slam_chess_candidates_dev(slam_ctx* ctx, void* stream, const uint8_t* d_frames, int nframes, int w, int h,
+                              int channels, int32_t* out, int cap, int32_t* n_out, int* scale);
+/* Host only, no device: the board_w * board_h strongest of n candidates (ties to
+ * the lower raster index) labelled as a complete lattice.  corners: board_w *
+ * board_h x 2 f32 in full-resolution pixels (scale * x + (scale - 1) / 2), row-major
+ * with rows of board_w, right-handed in image coordinates, first corner with the
+ * least x + y (ties: least y).  *found = 0 when they are no complete board. */
+int slam_label_chessboard(const int32_t* cand, int n, int scale, int board_w, int board_h, float* corners,
+                          int* found);
+/* findChessboardCorners(gray, Size(board_w, board_h), corners) of a host frame:
+ * slam_chess_candidates, then slam_label_chessboard. */
+int slam_find_chessboard(slam_ctx* ctx, const uint8_t* img, int w, int h, size_t step, int channels, int board_w,
+                         int board_h, float* corners, int* found);
+/* the same for nframes resident frames: corners nframes x board_w * board_h x 2,
+ * found nframes flags (host) */
+int slam_find_chessboard_dev(slam_ctx* ctx, void* stream, const uint8_t* d_frames, int nframes, int w, int h,
+                             int channels, int board_w, int board_h, float* corners, int32_t* found);
+/* cv::cornerSubPix(gray, corners, Size(win_w, win_h), Size(zero_w, zero_h),
+ * TermCriteria(COUNT + EPS, max_iter, eps)) of n corners (host, n x 2 f32, refined
+ * in place) on a host frame (channels 1 or 3: the gray FAST sees).  win 1..15 per
+ * axis; only the zero zone (-1, -1) is supported (SLAM_E_UNSUPPORTED otherwise);
+ * max_iter is clamped to 1..100 as OpenCV does; a start corner outside the image
+ * is SLAM_E_INVALID_ARG.  n == 0: SLAM_OK, no launch. */
+int slam_corner_subpix(slam_ctx* ctx, const uint8_t* img, int w, int h, size_t step, int channels, float* corners,
+                       int n, int win_w, int win_h, int zero_w, int zero_h, int max_iter, double eps);
+/* the same on one frame resident in HBM (row stride `step`); corners stay in host
+ * memory; synchronous */
+int slam_corner_subpix_dev(slam_ctx* ctx, void* stream, const uint8_t* d_img, int w, int h, size_t step,
+                           int channels, float* corners, int n, int win_w, int win_h, int zero_w, int zero_h,
+                           int max_iter, double eps);
+/* Host only, f64: the optimum of calibrateCamera(obj, img, Size(size_w, size_h), K,
+ * D, R, T) with default flags: fx fy cx cy, k1 k2 p1 p2 k3 and a rotation vector
+ * and translation per view.  obj: npts x 3 f32 with z = 0 (one board for all
+ * views); img: nviews x npts x 2 f32.  K 9, D 5, rvecs / tvecs nviews x 3 doubles;
+ * *rms = sqrt(sum |r|^2 / (nviews * npts)).  The size moves only the initial
+ * principal point.  nviews < 3, npts < 4 or z != 0: SLAM_E_INVALID_ARG; points
+ * that give no homography or focal length: SLAM_E_SOLVER. */
+int slam_calibrate_camera(const float* obj, const float* img, int nviews, int npts, int size_w, int size_h,
+                          double* K, double* D, double* rvecs, double* tvecs, double* rms, int* iterations);
+
 /* ---- options ------------------------------------------------------------------ */
 /* Per-context choices; all but SLAM_OPT_PNP_SUMS (below) never change results.  SLAM_OPT_SIFT_KERNEL picks the
  * kernel for SIFT descriptors of keypoints sharing one angle and size (FAST

@@ -419,7 +419,8 @@ void slam_destroy(slam_ctx* c)
                       &c->match_cnt, &c->match_out, &c->frames_in, &c->qbuf, &c->tbuf, &c->misc, &c->ba_obs,
                       &c->ba_par, &c->ba_jac, &c->ba_red, &c->ba_S, &c->ba_aux, &c->sd_pyr, &c->sd_cand,
                       &c->sd_kps, &c->sd_kpc, &c->sift_tab, &c->sift_band_buf, &c->sift_cols_buf, &c->sift_cols_park, &c->sift_colw_buf, &c->sift_split, &c->sift_split_cnt, &c->sift_deal, &c->geom, &c->cluster, &c->delaunay,
-                      &c->undist_xy, &c->undist_frac, &c->undist_out, &c->undist_pts};
+                      &c->undist_xy, &c->undist_frac, &c->undist_out, &c->undist_pts,
+                      &c->calib_resp, &c->calib_mask, &c->calib_out, &c->calib_sub};
     for (DevBuf* b : bufs) b->release();
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->ev_up) (void)hipEventDestroy(c->ev_up);
@@ -1308,6 +1309,210 @@ int slam_undistort_points(slam_ctx* c, const float* src, size_t src_stride, int 
     SLAM_HIP(c, hipMemcpyAsync(dst, d_dst, sb, hipMemcpyDeviceToHost, c->stream));
     if (err) SLAM_HIP(c, hipMemcpyAsync(err, d_err, se, hipMemcpyDeviceToHost, c->stream));
     return stream_sync(c, c->stream);
+}
+
+// ---- chessboard calibration (calib.hip, calib_board.cpp, calib_solve.cpp) ----
+
+// candidates of nframes resident frames to host memory: out nframes x cap x 3, n_out nframes
+static int chess_candidates_run(slam_ctx* c, hipStream_t s, const uint8_t* d_img, size_t frame_stride, size_t row_stride,
+                                int channels, int nframes, int w, int h, int32_t* out, int cap, int32_t* n_out, int* scale)
+{
+    if (w > 65535 || h > 65535 || nframes > 65535)
+        return set_err(c, SLAM_E_UNSUPPORTED, "chess candidates: frame or batch too large");
+    if (scale) *scale = chess_scale(w, h);
+    const int dcap = chess_cap(w, h);
+    SLAM_HIP(c, launch_chess_candidates(c, s, d_img, frame_stride, row_stride, channels, nframes, w, h));
+    const int32_t* d_out = c->calib_out.as<int32_t>();
+    SLAM_HIP(c, hipMemcpyAsync(n_out, d_out + (size_t)nframes * dcap * 3, (size_t)nframes * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, s));
+    if (int rc = stream_sync(c, s)) return rc;
+    bool fits = true;
+    for (int f = 0; f < nframes; f++) fits = fits && n_out[f] <= cap && n_out[f] <= dcap;
+    if (!fits) return set_err(c, SLAM_E_CAPACITY, "candidate buffer too small");
+    for (int f = 0; f < nframes; f++)
+        if (n_out[f] > 0)
+            SLAM_HIP(c, hipMemcpyAsync(out + (size_t)f * cap * 3, d_out + (size_t)f * dcap * 3,
+                                       (size_t)n_out[f] * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    return stream_sync(c, s);
+}
+
+static int chess_args(slam_ctx* c, int w, int h, int channels)
+{
+    if (w <= 0 || h <= 0 || (channels != 1 && channels != 3))
+        return set_err(c, SLAM_E_INVALID_ARG, "chessboard: an 8-bit frame with 1 or 3 channels");
+    return SLAM_OK;
+}
+
+int slam_chess_candidates(slam_ctx* c, const uint8_t* img, int w, int h, size_t step, int channels, int32_t* out, int cap,
+                          int* n_out, int* scale)
+{
+    if (!c || !n_out || cap < 0 || (cap > 0 && !out)) return SLAM_E_INVALID_ARG;
+    if (int rc = async_guard(c)) return rc;
+    if (int rc = chess_args(c, w, h, channels)) return rc;
+    if (!img || step < (size_t)w * channels) return set_err(c, SLAM_E_INVALID_ARG, "chessboard: null frame or short row stride");
+    SLAM_HIP(c, hipSetDevice(c->device));
+    const uint8_t* dimg;
+    size_t dstep;
+    if (int rc = upload_image(c, img, w, h, step, channels, &dimg, &dstep)) return rc;
+    int32_t n = 0;
+    const int rc = chess_candidates_run(c, c->stream, dimg, dstep * h, dstep, channels, 1, w, h, out, cap, &n, scale);
+    *n_out = n;
+    return rc;
+}
+
+int slam_chess_candidates_dev(slam_ctx* c, void* stream, const uint8_t* d_frames, int nframes, int w, int h, int channels,
+                              int32_t* out, int cap, int32_t* n_out, int* scale)
+{
+    if (!c || nframes < 0 || cap < 0 || (nframes > 0 && (!n_out || !d_frames || (cap > 0 && !out)))) return SLAM_E_INVALID_ARG;
+    if (int rc = chess_args(c, w, h, channels)) return rc;
+    if (scale) *scale = chess_scale(w, h);
+    if (nframes == 0) return SLAM_OK;
+    SLAM_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    const size_t row = (size_t)w * channels;
+    return chess_candidates_run(c, s, d_frames, row * h, row, channels, nframes, w, h, out, cap, n_out, scale);
+}
+
+int slam_label_chessboard(const int32_t* cand, int n, int scale, int board_w, int board_h, float* corners, int* found)
+{
+    if (!found || !corners || n < 0 || (n > 0 && !cand) || scale < 1 || board_w < 2 || board_h < 2 ||
+        (long long)board_w * board_h > 4096)
+        return SLAM_E_INVALID_ARG;
+    *found = label_chessboard(cand, n, scale, board_w, board_h, corners) ? 1 : 0;
+    return SLAM_OK;
+}
+
+static int find_chessboard_run(slam_ctx* c, hipStream_t s, const uint8_t* d_img, size_t row_stride, int channels,
+                               int nframes, int w, int h, int board_w, int board_h, float* corners, int32_t* found)
+{
+    const int cap = chess_cap(w, h);
+    std::vector<int32_t> cand((size_t)nframes * cap * 3), cnt(nframes);
+    int scale = 1;
+    if (int rc = chess_candidates_run(c, s, d_img, row_stride * h, row_stride, channels, nframes, w, h, cand.data(), cap,
+                                      cnt.data(), &scale))
+        return rc;
+    const size_t per = (size_t)board_w * board_h * 2;
+    for (int f = 0; f < nframes; f++)
+        found[f] = label_chessboard(cand.data() + (size_t)f * cap * 3, cnt[f], scale, board_w, board_h, corners + f * per) ? 1 : 0;
+    return SLAM_OK;
+}
+
+int slam_find_chessboard(slam_ctx* c, const uint8_t* img, int w, int h, size_t step, int channels, int board_w,
+                         int board_h, float* corners, int* found)
+{
+    if (!c || !corners || !found) return SLAM_E_INVALID_ARG;
+    if (int rc = async_guard(c)) return rc;
+    if (int rc = chess_args(c, w, h, channels)) return rc;
+    if (!img || step < (size_t)w * channels) return set_err(c, SLAM_E_INVALID_ARG, "chessboard: null frame or short row stride");
+    if (board_w < 2 || board_h < 2 || (long long)board_w * board_h > 4096)
+        return set_err(c, SLAM_E_INVALID_ARG, "chessboard: a board has at least 2 x 2 and at most 4096 inner corners");
+    SLAM_HIP(c, hipSetDevice(c->device));
+    const uint8_t* dimg;
+    size_t dstep;
+    if (int rc = upload_image(c, img, w, h, step, channels, &dimg, &dstep)) return rc;
+    int32_t f = 0;
+    const int rc = find_chessboard_run(c, c->stream, dimg, dstep, channels, 1, w, h, board_w, board_h, corners, &f);
+    *found = f;
+    return rc;
+}
+
+int slam_find_chessboard_dev(slam_ctx* c, void* stream, const uint8_t* d_frames, int nframes, int w, int h, int channels,
+                             int board_w, int board_h, float* corners, int32_t* found)
+{
+    if (!c || nframes < 0 || (nframes > 0 && (!d_frames || !corners || !found))) return SLAM_E_INVALID_ARG;
+    if (int rc = chess_args(c, w, h, channels)) return rc;
+    if (board_w < 2 || board_h < 2 || (long long)board_w * board_h > 4096)
+        return set_err(c, SLAM_E_INVALID_ARG, "chessboard: a board has at least 2 x 2 and at most 4096 inner corners");
+    if (nframes == 0) return SLAM_OK;
+    SLAM_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    return find_chessboard_run(c, s, d_frames, (size_t)w * channels, channels, nframes, w, h, board_w, board_h, corners,
+                               found);
+}
+
+// cornerSubPix of host corners on a resident frame
+static int corner_subpix_run(slam_ctx* c, hipStream_t s, const uint8_t* d_img, int w, int h, size_t step, int channels,
+                             float* corners, int n, int win_w, int win_h, int max_iter, double eps)
+{
+    // the mask's factors exp(-x^2), x = (float)(j - w) / w, as (float)exp((double)(-x * x)) on the host:
+    // the same value in glibc and numpy (OpenCV's expf may differ by one ulp)
+    float tab[2 * (2 * kSubpixMaxWin + 1)];
+    const int ww = 2 * win_w + 1, wh = 2 * win_h + 1;
+    for (int j = 0; j < ww; j++) {
+        const float x = (float)(j - win_w) / (float)win_w;
+        tab[j] = (float)std::exp((double)(-x * x));
+    }
+    for (int i = 0; i < wh; i++) {
+        const float y = (float)(i - win_h) / (float)win_h;
+        tab[ww + i] = (float)std::exp((double)(-y * y));
+    }
+    const size_t cb = (size_t)n * 2 * sizeof(float);
+    SLAM_HIP(c, c->calib_sub.ensure(cb + sizeof(tab)));
+    float* d_corners = c->calib_sub.as<float>();
+    float* d_tab = d_corners + (size_t)n * 2;
+    SLAM_HIP(c, hipMemcpyAsync(d_corners, corners, cb, hipMemcpyHostToDevice, s));
+    SLAM_HIP(c, hipMemcpyAsync(d_tab, tab, (size_t)(ww + wh) * sizeof(float), hipMemcpyHostToDevice, s));
+    // the upload of `tab` (a stack array) must have left it before this function returns: the sync below
+    SLAM_HIP(c, launch_calib_subpix(s, d_img, step, channels, w, h, d_corners, n, win_w, win_h, max_iter, eps, d_tab,
+                                    d_tab + ww));
+    SLAM_HIP(c, hipMemcpyAsync(corners, d_corners, cb, hipMemcpyDeviceToHost, s));
+    return stream_sync(c, s);
+}
+
+static int corner_subpix_args(slam_ctx* c, int w, int h, size_t step, int channels, const float* corners, int n, int win_w,
+                              int win_h, int zero_w, int zero_h, int* max_iter, double* eps)
+{
+    if (int rc = chess_args(c, w, h, channels)) return rc;
+    if (step < (size_t)w * channels) return set_err(c, SLAM_E_INVALID_ARG, "cornerSubPix: short row stride");
+    if (n < 0 || (n > 0 && !corners)) return set_err(c, SLAM_E_INVALID_ARG, "cornerSubPix: null corners");
+    if (zero_w != -1 || zero_h != -1) return set_err(c, SLAM_E_UNSUPPORTED, "cornerSubPix: only the zero zone (-1, -1)");
+    if (win_w < 1 || win_h < 1) return set_err(c, SLAM_E_INVALID_ARG, "cornerSubPix: the half window is at least 1 per axis");
+    if (win_w > kSubpixMaxWin || win_h > kSubpixMaxWin)
+        return set_err(c, SLAM_E_UNSUPPORTED, "cornerSubPix: the half window is at most 15 per axis");
+    if (!(*eps == *eps)) return set_err(c, SLAM_E_INVALID_ARG, "cornerSubPix: eps is a number");
+    *eps = std::max(*eps, 0.0);
+    *max_iter = std::min(std::max(*max_iter, 1), 100);
+    for (int i = 0; i < n; i++) {
+        const float x = corners[2 * i], y = corners[2 * i + 1];
+        if (!(x >= 0.f && x < (float)w && y >= 0.f && y < (float)h))
+            return set_err(c, SLAM_E_INVALID_ARG, "cornerSubPix: a start corner outside the image");
+    }
+    return SLAM_OK;
+}
+
+int slam_corner_subpix(slam_ctx* c, const uint8_t* img, int w, int h, size_t step, int channels, float* corners, int n,
+                       int win_w, int win_h, int zero_w, int zero_h, int max_iter, double eps)
+{
+    if (!c) return SLAM_E_INVALID_ARG;
+    if (int rc = async_guard(c)) return rc;
+    if (int rc = corner_subpix_args(c, w, h, step, channels, corners, n, win_w, win_h, zero_w, zero_h, &max_iter, &eps))
+        return rc;
+    if (!img) return set_err(c, SLAM_E_INVALID_ARG, "cornerSubPix: null frame");
+    if (n == 0) return SLAM_OK;
+    SLAM_HIP(c, hipSetDevice(c->device));
+    const uint8_t* dimg;
+    size_t dstep;
+    if (int rc = upload_image(c, img, w, h, step, channels, &dimg, &dstep)) return rc;
+    return corner_subpix_run(c, c->stream, dimg, w, h, dstep, channels, corners, n, win_w, win_h, max_iter, eps);
+}
+
+int slam_corner_subpix_dev(slam_ctx* c, void* stream, const uint8_t* d_img, int w, int h, size_t step, int channels,
+                           float* corners, int n, int win_w, int win_h, int zero_w, int zero_h, int max_iter, double eps)
+{
+    if (!c) return SLAM_E_INVALID_ARG;
+    if (int rc = corner_subpix_args(c, w, h, step, channels, corners, n, win_w, win_h, zero_w, zero_h, &max_iter, &eps))
+        return rc;
+    if (!d_img) return set_err(c, SLAM_E_INVALID_ARG, "cornerSubPix: null frame");
+    if (n == 0) return SLAM_OK;
+    SLAM_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    return corner_subpix_run(c, s, d_img, w, h, step, channels, corners, n, win_w, win_h, max_iter, eps);
+}
+
+int slam_calibrate_camera(const float* obj, const float* img, int nviews, int npts, int size_w, int size_h, double* K,
+                          double* D, double* rvecs, double* tvecs, double* rms, int* iterations)
+{
+    return calibrate_camera(obj, img, nviews, npts, size_w, size_h, K, D, rvecs, tvecs, rms, iterations);
 }
 
 void* slam_context_stream(slam_ctx* c) { return c ? (void*)c->stream : nullptr; }

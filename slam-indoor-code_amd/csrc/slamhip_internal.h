@@ -37,6 +37,10 @@ constexpr int kFastTileW = 64, kFastTileH = 16;
 // undist_remap (undistort.hip): a workgroup owns one destination tile of
 // kUndistTileW x kUndistTileH pixels and loops over up to kUndistFrames frames
 constexpr int kUndistTileW = 128, kUndistTileH = 8, kUndistFrames = 8;
+// chess_response / chess_nms (calib.hip): level tiles of 64 columns (one wave, one
+// ballot per row) x 16 rows; calib_subpix: the largest half window per axis
+constexpr int kChessTileW = 64, kChessTileH = 16;
+constexpr int kSubpixMaxWin = 15;
 
 struct SiftConsts {
     float gauss[16];   // 13-tap kernel of GaussianBlur(sigma = sig_diff)
@@ -284,6 +288,10 @@ struct slam_ctx {
     hipStream_t undist_stream = nullptr;  // the stream that last built or read the map
     hipEvent_t undist_ev = nullptr;       // ... and the end of that work on it
 
+    // chessboard calibration (calib.hip): response maps, NMS masks, candidates +
+    // counts, and cornerSubPix's corners + mask factors
+    slamhip::DevBuf calib_resp, calib_mask, calib_out, calib_sub;
+
     bool prof_on = false;
     slamhip::ProfFamily prof[8];
     // slam_set_option: which SIFT descriptor kernel runs (all bit-identical)
@@ -476,6 +484,27 @@ int undist_points_params(slam_ctx* c, const double* K, const double* dist, int n
 // n > 0 points read at src + i * src_stride; dst n x 2 packed, err n or null; dst == src allowed at stride 8
 hipError_t launch_undist_points(hipStream_t s, const UndistPointsParams& P, const float* src, size_t src_stride, int n,
                                 float* dst, float* err);
+
+// ---- chessboard calibration (calib.hip, calib_board.cpp, calib_solve.cpp) ----
+// the level's downscale s = max(1, ceil(max(w, h) / 1024)) and the candidate bound
+// ceil(W / 8) * ceil(H / 8) of a W x H level (two candidates are never within
+// Chebyshev distance 7 of each other)
+int chess_scale(int w, int h);
+int chess_cap(int w, int h);
+// candidates of nframes frames (frame f at img + f * frame_stride) into
+// c->calib_out: nframes x chess_cap x 3 int32 (x, y, R) in raster order, then nframes counts
+hipError_t launch_chess_candidates(slam_ctx* c, hipStream_t s, const uint8_t* img, size_t frame_stride,
+                                   size_t row_stride, int channels, int nframes, int w, int h);
+// cornerSubPix of n > 0 corners (device, n x 2 f32, in place); d_vx / d_vy: the mask's factors
+hipError_t launch_calib_subpix(hipStream_t s, const uint8_t* img, size_t row_stride, int channels, int w, int h,
+                               float* d_corners, int n, int win_w, int win_h, int max_iter, double eps,
+                               const float* d_vx, const float* d_vy);
+// the board_w * board_h strongest of n candidates labelled as a lattice (calib_board.cpp):
+// corners in full-resolution pixels, canonical order; false: no complete board
+bool label_chessboard(const int32_t* cand, int n, int scale, int board_w, int board_h, float* corners);
+// calibrateCamera's optimum (calib_solve.cpp); returns a SLAM_* code
+int calibrate_camera(const float* obj, const float* img, int nviews, int npts, int size_w, int size_h, double* K,
+                     double* D, double* rvecs, double* tvecs, double* rms, int* iterations);
 
 // ---- BA (ba.hip) ----
 int ba_solve(slam_ctx* c, double* K4, int nframes, double* ext6, int npoints, double* pts3, int nobs,

@@ -20,7 +20,10 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
                   SYNTH_DRIFT, SYNTH_STEADY, synth_frames_dev,
                   clusterizePoints, clusterLabels, getBestFittingPlaneByPoints, planeMoments, projectToPlane,
                   delaunay2d, delaunay2dHost, delaunayStats, delaunayPredicates, meshFilter,
-                  load_calibration, undistort, undistortBatch, undistortMap, undistortPoints)
+                  load_calibration, undistort, undistortBatch, undistortMap, undistortPoints,
+                  chessCandidates, labelChessboard, findChessboardCorners, cornerSubPix, calibrateCamera,
+                  save_calibration)
 from .config import ConfigError, ConfigService, reference_example
+from .calibration import CalibrationError, chessboard_photos_calibration
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -776,6 +776,164 @@ def undistortPoints(pts_or_keypoints, K, dist, P=None, criteria=(5, 0.0), ctx=No
     return xy, err
 
 
+# ---- chessboard calibration (the reference's "calibrate" mode) -------------------
+
+def _frame13(frame):
+    a = np.asarray(frame)
+    if a.dtype != np.uint8:
+        raise TypeError("frames are 8-bit (CV_8UC1/3)")
+    if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
+        raise ValueError("frame must be HxW or HxWx3 (BGR)")
+    ch = 1 if a.ndim == 2 else 3
+    if a.strides[1:] != ((1,) if ch == 1 else (3, 1)) or a.strides[0] < a.shape[1] * ch:
+        a = np.ascontiguousarray(a)
+    return a, a.shape[1], a.shape[0], ch
+
+
+def _resident(frames):
+    import torch
+    if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or (frames.dim() == 4 and frames.shape[3] != 3):
+        raise ValueError("frames: uint8 (n, h, w) or (n, h, w, 3)")
+    if not frames.is_contiguous():
+        frames = frames.contiguous()
+    torch.cuda.current_stream(frames.device).synchronize()    # the frames' producer
+    return frames, int(frames.shape[0]), int(frames.shape[2]), int(frames.shape[1]), 1 if frames.dim() == 3 else 3
+
+
+def chessCap(w, h):
+    """the most candidates a w x h frame can have: ceil(W / 8) * ceil(H / 8) of its level"""
+    s = max(1, -(-max(w, h) // 1024))
+    return -(-(w // s) // 8) * -(-(h // s) // 8)
+
+
+def chessCandidates(frame, ctx=None):
+    """chessboard corner candidates (slam_chess_candidates): (cand, s) with cand
+    (n, 3) int32 rows (x, y, R) in raster order, in the coordinates of the level
+    image: the s x s area mean of the gray frame, s = max(1, ceil(max(w, h) / 1024)).
+    R is 80 x the ChESS response; a candidate is the maximum of its 15 x 15 window.
+    `frame`: a host array, or a resident torch batch (n, h, w[, 3]) -> a list of n
+    arrays from one launch per kernel (slam_chess_candidates_dev)."""
+    ctx = ctx or default_context()
+    c = ctx.handle
+    s = ctypes.c_int(0)
+    if not isinstance(frame, np.ndarray) and hasattr(frame, "data_ptr"):
+        fr, n, w, h, ch = _resident(frame)
+        cap = chessCap(w, h)
+        out = np.empty((n, cap, 3), np.int32)
+        cnt = np.zeros(n, np.int32)
+        check(lib().slam_chess_candidates_dev(c, None, ctypes.c_void_p(fr.data_ptr()), n, w, h, ch, ptr(out), cap,
+                                              ptr(cnt), ctypes.byref(s)), c)
+        return [out[f, :cnt[f]].copy() for f in range(n)], s.value
+    a, w, h, ch = _frame13(frame)
+    cap = chessCap(w, h)
+    out = np.empty((cap, 3), np.int32)
+    n = ctypes.c_int(0)
+    check(lib().slam_chess_candidates(c, ptr(a), w, h, a.strides[0], ch, ptr(out), cap, ctypes.byref(n),
+                                      ctypes.byref(s)), c)
+    return out[:n.value].copy(), s.value
+
+
+def labelChessboard(cand, scale, patternSize):
+    """slam_label_chessboard (host only): the patternSize[0] * patternSize[1]
+    strongest candidates as a complete board -> (found, corners (n, 2) float32 in
+    full-resolution pixels, canonical order) or (False, None)."""
+    bw, bh = int(patternSize[0]), int(patternSize[1])
+    cand = np.ascontiguousarray(cand, np.int32).reshape(-1, 3)
+    corners = np.empty((bw * bh, 2), np.float32)
+    found = ctypes.c_int(0)
+    check(lib().slam_label_chessboard(ptr(cand), len(cand), int(scale), bw, bh, ptr(corners), ctypes.byref(found)))
+    return (True, corners) if found.value else (False, None)
+
+
+def findChessboardCorners(frame, patternSize, ctx=None):
+    """findChessboardCorners(gray, patternSize, corners) (cameraCalibration.cpp:168)
+    by this library's own detector: (found, corners) with corners (w * h, 2) float32
+    in pixels, row-major with rows of patternSize[0], right-handed in image
+    coordinates, first corner nearest the image's origin; (False, None) when the
+    strongest candidates are not a complete board.  A resident torch batch
+    (n, h, w[, 3]) gives a list of n such pairs (slam_find_chessboard_dev)."""
+    ctx = ctx or default_context()
+    c = ctx.handle
+    bw, bh = int(patternSize[0]), int(patternSize[1])
+    if not isinstance(frame, np.ndarray) and hasattr(frame, "data_ptr"):
+        fr, n, w, h, ch = _resident(frame)
+        corners = np.empty((n, bw * bh, 2), np.float32)
+        found = np.zeros(n, np.int32)
+        check(lib().slam_find_chessboard_dev(c, None, ctypes.c_void_p(fr.data_ptr()), n, w, h, ch, bw, bh, ptr(corners),
+                                             ptr(found)), c)
+        return [(True, corners[f].copy()) if found[f] else (False, None) for f in range(n)]
+    a, w, h, ch = _frame13(frame)
+    corners = np.empty((bw * bh, 2), np.float32)
+    found = ctypes.c_int(0)
+    check(lib().slam_find_chessboard(c, ptr(a), w, h, a.strides[0], ch, bw, bh, ptr(corners), ctypes.byref(found)), c)
+    return (True, corners) if found.value else (False, None)
+
+
+def cornerSubPix(frame, corners, winSize=(11, 11), criteria=(30, 1e-4), zeroZone=(-1, -1), ctx=None):
+    """cv::cornerSubPix(gray, corners, winSize, zeroZone, TermCriteria(COUNT + EPS,
+    *criteria)) (cameraCalibration.cpp:169) on the device; returns the refined
+    (n, 2) float32 corners.  `frame`: a host array or one resident torch frame
+    (h, w[, 3]).  Only zeroZone (-1, -1); winSize at most (15, 15)."""
+    ctx = ctx or default_context()
+    c = ctx.handle
+    out = np.array(corners, np.float32).reshape(-1, 2).copy()
+    max_iter, eps = criteria
+    tail = (len(out), int(winSize[0]), int(winSize[1]), int(zeroZone[0]), int(zeroZone[1]), int(max_iter), float(eps))
+    if not isinstance(frame, np.ndarray) and hasattr(frame, "data_ptr"):
+        fr, _, w, h, ch = _resident(frame[None])
+        check(lib().slam_corner_subpix_dev(c, None, ctypes.c_void_p(fr.data_ptr()), w, h, w * ch, ch, ptr(out), *tail), c)
+        return out
+    a, w, h, ch = _frame13(frame)
+    check(lib().slam_corner_subpix(c, ptr(a), w, h, a.strides[0], ch, ptr(out), *tail), c)
+    return out
+
+
+def calibrateCamera(objectPoints, imagePoints, imageSize):
+    """calibrateCamera(objectPoints, imagePoints, imageSize, K, D, R, T) with default
+    flags (cameraCalibration.cpp:196), on the host in f64: the optimum of the
+    reprojection error over fx fy cx cy, k1 k2 p1 p2 k3 and a pose per view (not
+    OpenCV's iterate after 30 steps).  objectPoints: (npts, 3) with z = 0, one
+    board for all views; imagePoints: (nviews, npts, 2); imageSize (width, height)
+    only places the initial principal point.  Returns (rms, K 3x3, D (5,), rvecs
+    (nviews, 3), tvecs (nviews, 3))."""
+    obj = np.ascontiguousarray(objectPoints, np.float32)
+    if obj.ndim == 3:
+        if any(not np.array_equal(o, obj[0]) for o in obj):
+            raise ValueError("one board for all views")
+        obj = np.ascontiguousarray(obj[0])
+    img = np.ascontiguousarray(imagePoints, np.float32)
+    if obj.ndim != 2 or obj.shape[1] != 3 or img.ndim != 3 or img.shape[1:] != (len(obj), 2):
+        raise ValueError("objectPoints (npts, 3), imagePoints (nviews, npts, 2)")
+    nv = len(img)
+    K, D = np.zeros((3, 3)), np.zeros(5)
+    rv, tv = np.zeros((nv, 3)), np.zeros((nv, 3))
+    rms = ctypes.c_double(0)
+    it = ctypes.c_int(0)
+    check(lib().slam_calibrate_camera(ptr(obj), ptr(img), nv, len(obj), int(imageSize[0]), int(imageSize[1]), ptr(K),
+                                      ptr(D), ptr(rv), ptr(tv), ctypes.byref(rms), ctypes.byref(it)))
+    return rms.value, K, D, rv, tv
+
+
+def save_calibration(path, K, D, R, T):
+    """saveCalibParametersToXML (IOmisc.cpp:68-76): K 3x3 "d", DC 1x5 "d", R and T
+    Nx1 "3d" in OpenCV's XML storage, doubles as %.16e: load_calibration reads each
+    key back bit for bit."""
+    def node(name, rows, cols, dt, data):
+        vals = " ".join("%.16e" % float(v) for v in np.asarray(data, np.float64).ravel())
+        return (f'<{name} type_id="opencv-matrix">\n  <rows>{rows}</rows>\n  <cols>{cols}</cols>\n'
+                f'  <dt>{dt}</dt>\n  <data>\n    {vals}</data></{name}>\n')
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    D = np.asarray(D, np.float64).reshape(-1)
+    R = np.asarray(R, np.float64).reshape(-1, 3)
+    T = np.asarray(T, np.float64).reshape(-1, 3)
+    if len(R) != len(T):
+        raise ValueError("one rotation and one translation per view")
+    text = ('<?xml version="1.0"?>\n<opencv_storage>\n' + node("K", 3, 3, "d", K) + node("DC", 1, D.size, "d", D) +
+            node("R", len(R), 1, '"3d"', R) + node("T", len(T), 1, '"3d"', T) + "</opencv_storage>\n")
+    with open(path, "w") as f:
+        f.write(text)
+
+
 SYNTH_DRIFT, SYNTH_STEADY = 0, 1
 
 
