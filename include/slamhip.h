@@ -599,6 +599,66 @@ int slam_corner_subpix_dev(slam_ctx* ctx, void* stream, const uint8_t* d_img, in
 int slam_calibrate_camera(const float* obj, const float* img, int nviews, int npts, int size_w, int size_h,
                           double* K, double* D, double* rvecs, double* tvecs, double* rms, int* iterations);
 
+/* ---- pyramidal Lucas-Kanade tracking ------------------------------------------------ */
+/* The reference's second front-end mode (README.md:173 "useFeatureTracker",
+ * docs/artifact/2dWorldPoseRefining.md): frame-to-frame tracking of keypoints
+ * without descriptors, cv::calcOpticalFlowPyrLK over cv::buildOpticalFlowPyramid
+ * (OpenCV 4.8, lkpyramid.cpp / pyramids.cpp), on one 8-bit channel: frames with 3
+ * or 4 channels are tracked on the gray FAST sees.  tests/klt_ref.py defines every
+ * value; DESIGN.md section 15 has the contract.
+ *
+ * One deliberate deviation: the five window sums of a point (Ix^2, Ix Iy, Iy^2,
+ * diff Ix, diff Iy: integer terms below 2^26) are exact.  OpenCV adds them into
+ * f32 accumulators in an order that differs between its scalar, SSE and AVX
+ * builds, which therefore disagree in the last bits; here they are summed in
+ * int64 and converted to f32 once, round to nearest even, before the 2^-20
+ * scale.  Everything downstream is f32 in the source's order.  Further: reads
+ * outside a level reflect (101) for intensities at any distance and are 0 for
+ * derivatives; a window position whose floor is not an int (NaN, infinite, beyond
+ * the int range) is outside; err of a point that no level wrote is 0.
+ *
+ * Parameters: win_w, win_h in 3..31; max_level 0..8; max_count >= 1 (clamped to
+ * 100 as OpenCV does) and eps >= 0 (clamped to 10) of TermCriteria(COUNT + EPS);
+ * flags: SLAM_KLT_USE_INITIAL_FLOW | SLAM_KLT_GET_MIN_EIGENVALS.  Anything else,
+ * a null pointer that is needed, channels other than 1, 3, 4 or a short row step:
+ * SLAM_E_INVALID_ARG.  n == 0 succeeds.
+ *
+ * slam_klt_pyramid (cv::buildOpticalFlowPyramid + calcScharrDeriv): the levels of a
+ * host frame.  *nlevels: the number of levels built (max_level + 1, or fewer when
+ * the next level would be no larger than the window); sizes: nlevels x (w, h);
+ * gray: the levels' pixels packed one after another, unpadded; deriv (or NULL):
+ * int16 {Ix, Iy} per pixel, the same packing.  cap_pixels: the room in gray (and
+ * deriv / 2); SLAM_E_CAPACITY with *need_pixels set when it is too small. */
+enum slam_klt_flags { SLAM_KLT_USE_INITIAL_FLOW = 4, SLAM_KLT_GET_MIN_EIGENVALS = 8 };
+int slam_klt_pyramid(slam_ctx* ctx, const uint8_t* img, int w, int h, size_t step, int channels, int win_w, int win_h,
+                     int max_level, int* nlevels, int32_t* sizes, uint8_t* gray, int16_t* deriv, size_t cap_pixels,
+                     size_t* need_pixels);
+/* cv::calcOpticalFlowPyrLK(prev, next, prevPts, nextPts, status, err, Size(win_w,
+ * win_h), max_level, TermCriteria(COUNT + EPS, max_count, eps), flags, min_eig) on
+ * two host frames of one size.  prev_pts, next_pts: n x 2 f32 (next_pts is read
+ * with SLAM_KLT_USE_INITIAL_FLOW); status n u8; err n f32; all host, synchronous. */
+int slam_klt_track(slam_ctx* ctx, const uint8_t* prev, size_t prev_step, const uint8_t* next, size_t next_step, int w,
+                   int h, int channels, const float* prev_pts, int n, float* next_pts, uint8_t* status, float* err,
+                   int win_w, int win_h, int max_level, int max_count, double eps, int flags, double min_eig);
+/* the same on two frames resident in HBM (row stride `step`), on `stream` (NULL =
+ * the context stream); points and results stay in host memory; synchronous */
+int slam_klt_track_dev(slam_ctx* ctx, void* stream, const uint8_t* d_prev, const uint8_t* d_next, int w, int h,
+                       size_t step, int channels, const float* prev_pts, int n, float* next_pts, uint8_t* status,
+                       float* err, int win_w, int win_h, int max_level, int max_count, double eps, int flags,
+                       double min_eig);
+/* one previous frame's points tracked into nframes packed resident candidates
+ * (nframes x h x w x channels) in one pass: one pyramid launch per level for the
+ * batch, one tracking launch.  next_pts nframes x n x 2, status nframes x n, err
+ * nframes x n (host; candidate f's rows equal slam_klt_track_dev on that frame;
+ * with SLAM_KLT_USE_INITIAL_FLOW next_pts is read and required, otherwise all three
+ * may be NULL together: only the counts are returned); counts (host, nframes):
+ * the number of status == 1 points per candidate.  The scratch (pyramids,
+ * derivative planes, points) is the context's, grown on demand.  Synchronous. */
+int slam_klt_track_batch_dev(slam_ctx* ctx, void* stream, const uint8_t* d_prev, const uint8_t* d_frames, int nframes,
+                             int w, int h, int channels, const float* prev_pts, int n, float* next_pts,
+                             uint8_t* status, float* err, int32_t* counts, int win_w, int win_h, int max_level,
+                             int max_count, double eps, int flags, double min_eig);
+
 /* ---- options ------------------------------------------------------------------ */
 /* Per-context choices; all but SLAM_OPT_PNP_SUMS (below) never change results.  SLAM_OPT_SIFT_KERNEL picks the
  * kernel for SIFT descriptors of keypoints sharing one angle and size (FAST
@@ -653,7 +713,7 @@ int slam_last_knn_launch(const slam_ctx* ctx, int* mode, int* tsplit, int* varia
 /* ---- profiling hooks (bench.py) ---------------------------------------------- */
 /* average duration (ms) of the last batch's launches of one kernel family,
  * measured with HIP events on the launch stream: 0 fast, 1 sift_desc, 2 knn,
- * 3 orb_desc, 4 sift_blur, 5 ratio/compact */
+ * 3 orb_desc, 4 sift_blur, 5 ratio/compact, 6 klt pyramids + derivatives, 7 klt_track */
 int slam_profile_enable(slam_ctx* ctx, int on);
 int slam_profile_read(slam_ctx* ctx, int family, double* avg_ms, int* launches);
 

@@ -420,7 +420,8 @@ void slam_destroy(slam_ctx* c)
                       &c->ba_par, &c->ba_jac, &c->ba_red, &c->ba_S, &c->ba_aux, &c->sd_pyr, &c->sd_cand,
                       &c->sd_kps, &c->sd_kpc, &c->sift_tab, &c->sift_band_buf, &c->sift_cols_buf, &c->sift_cols_park, &c->sift_colw_buf, &c->sift_split, &c->sift_split_cnt, &c->sift_deal, &c->geom, &c->cluster, &c->delaunay,
                       &c->undist_xy, &c->undist_frac, &c->undist_out, &c->undist_pts,
-                      &c->calib_resp, &c->calib_mask, &c->calib_out, &c->calib_sub};
+                      &c->calib_resp, &c->calib_mask, &c->calib_out, &c->calib_sub,
+                      &c->klt_img, &c->klt_pyr, &c->klt_deriv, &c->klt_pts};
     for (DevBuf* b : bufs) b->release();
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->ev_up) (void)hipEventDestroy(c->ev_up);
@@ -1887,6 +1888,196 @@ int slam_ba(slam_ctx* c, double* K4, int nframes, double* ext6, int npoints, dou
     int rc = ba_solve(c, K4, nframes, ext6, npoints, pts3, nobs, of, op, oxy, loss, a, max_iters, sum);
     sum->total_time_in_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return rc;
+}
+
+
+// ---- pyramidal Lucas-Kanade tracking (klt.hip) -----------------------------------
+
+struct KltArgs {
+    int win_w, win_h, max_level, max_count, flags;
+    double eps2;
+    float min_eig;
+};
+
+static int klt_args(slam_ctx* c, int w, int h, int channels, int win_w, int win_h, int max_level, int max_count,
+                    double eps, int flags, double min_eig, KltArgs* a)
+{
+    if (w <= 0 || h <= 0 || (channels != 1 && channels != 3 && channels != 4))
+        return set_err(c, SLAM_E_INVALID_ARG, "klt: an 8-bit frame with 1, 3 or 4 channels");
+    if ((long long)w * h > (1ll << 30)) return set_err(c, SLAM_E_INVALID_ARG, "klt: frame too large");
+    if (win_w < kKltMinWin || win_w > kKltMaxWin || win_h < kKltMinWin || win_h > kKltMaxWin)
+        return set_err(c, SLAM_E_INVALID_ARG, "klt: the window is 3..31 per axis");
+    if (max_level < 0 || max_level >= kKltMaxLevels) return set_err(c, SLAM_E_INVALID_ARG, "klt: maxLevel is 0..8");
+    if (max_count < 1 || !(eps >= 0)) return set_err(c, SLAM_E_INVALID_ARG, "klt: maxCount >= 1 and eps >= 0");
+    if (flags & ~(SLAM_KLT_USE_INITIAL_FLOW | SLAM_KLT_GET_MIN_EIGENVALS))
+        return set_err(c, SLAM_E_INVALID_ARG, "klt: flags are USE_INITIAL_FLOW (4) | GET_MIN_EIGENVALS (8)");
+    if (!(min_eig == min_eig)) return set_err(c, SLAM_E_INVALID_ARG, "klt: minEigThreshold is a number");
+    a->win_w = win_w;
+    a->win_h = win_h;
+    a->max_level = max_level;
+    // calcOpticalFlowPyrLK: maxCount clamped to 100, epsilon to 10, then squared (f64)
+    a->max_count = std::min(max_count, 100);
+    eps = std::min(eps, 10.0);
+    a->eps2 = eps * eps;
+    a->flags = flags;
+    a->min_eig = (float)min_eig;
+    return SLAM_OK;
+}
+
+// rows of a host frame into packed device memory (row = w * channels bytes)
+static int klt_upload(slam_ctx* c, hipStream_t s, uint8_t* dst, const uint8_t* img, size_t step, size_t row, int h)
+{
+    if (step == row) SLAM_HIP(c, hipMemcpyAsync(dst, img, row * h, hipMemcpyHostToDevice, s));
+    else SLAM_HIP(c, hipMemcpy2DAsync(dst, row, img, step, row, h, hipMemcpyHostToDevice, s));
+    return SLAM_OK;
+}
+
+int slam_klt_pyramid(slam_ctx* c, const uint8_t* img, int w, int h, size_t step, int channels, int win_w, int win_h,
+                     int max_level, int* nlevels, int32_t* sizes, uint8_t* gray, int16_t* deriv, size_t cap_pixels,
+                     size_t* need_pixels)
+{
+    if (!c || !nlevels || !sizes || !gray) return SLAM_E_INVALID_ARG;
+    if (int rc = async_guard(c)) return rc;
+    KltArgs a;
+    if (int rc = klt_args(c, w, h, channels, win_w, win_h, max_level, 1, 0.0, 0, 0.0, &a)) return rc;
+    if (!img || step < (size_t)w * channels) return set_err(c, SLAM_E_INVALID_ARG, "klt: null frame or short row stride");
+    const KltLayout L = klt_layout(w, h, win_w, win_h, max_level);
+    const size_t px = (size_t)L.off[L.nlevels - 1] + (size_t)L.w[L.nlevels - 1] * L.h[L.nlevels - 1];
+    if (need_pixels) *need_pixels = px;
+    *nlevels = L.nlevels;
+    if (px > cap_pixels) return set_err(c, SLAM_E_CAPACITY, "klt: level buffers too small");
+    SLAM_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t row = (size_t)w * channels;
+    SLAM_HIP(c, c->klt_img.ensure(row * h));
+    SLAM_HIP(c, c->klt_pyr.ensure(L.frame_px));
+    if (int rc = klt_upload(c, s, c->klt_img.as<uint8_t>(), img, step, row, h)) return rc;
+    SLAM_HIP(c, launch_klt_pyramid(s, c->klt_img.as<uint8_t>(), row * h, row, channels, 1, L, c->klt_pyr.as<uint8_t>()));
+    SLAM_HIP(c, hipMemcpyAsync(gray, c->klt_pyr.p, px, hipMemcpyDeviceToHost, s));
+    if (deriv) {
+        SLAM_HIP(c, c->klt_deriv.ensure((size_t)L.frame_px * 2 * sizeof(int16_t)));
+        SLAM_HIP(c, launch_klt_scharr(s, c->klt_pyr.as<uint8_t>(), L, c->klt_deriv.as<int16_t>()));
+        SLAM_HIP(c, hipMemcpyAsync(deriv, c->klt_deriv.p, px * 2 * sizeof(int16_t), hipMemcpyDeviceToHost, s));
+    }
+    for (int l = 0; l < L.nlevels; l++) {
+        sizes[2 * l] = L.w[l];
+        sizes[2 * l + 1] = L.h[l];
+    }
+    return stream_sync(c, s);
+}
+
+// d_prev / d_frames resident; points and results in host memory
+static int klt_run(slam_ctx* c, hipStream_t s, const uint8_t* d_prev, size_t prev_step, const uint8_t* d_frames,
+                   size_t frame_stride, size_t step, int nframes, int w, int h, int channels, const float* prev_pts, int n,
+                   float* next_pts, uint8_t* status, float* err, int32_t* counts, const KltArgs& a)
+{
+    const KltLayout L = klt_layout(w, h, a.win_w, a.win_h, a.max_level);
+    const size_t tot = (size_t)nframes * n;
+    // prev_pts | next_pts | err | counts | status
+    const size_t o_next = (size_t)n * 2 * sizeof(float), o_err = o_next + tot * 2 * sizeof(float),
+                 o_cnt = o_err + tot * sizeof(float), o_st = o_cnt + (size_t)nframes * sizeof(int32_t);
+    SLAM_HIP(c, c->klt_pts.ensure(o_st + tot));
+    SLAM_HIP(c, c->klt_pyr.ensure((size_t)(nframes + 1) * L.frame_px));
+    SLAM_HIP(c, c->klt_deriv.ensure((size_t)L.frame_px * 2 * sizeof(int16_t)));
+    uint8_t* base = c->klt_pts.as<uint8_t>();
+    float* d_prev_pts = reinterpret_cast<float*>(base);
+    float* d_next = reinterpret_cast<float*>(base + o_next);
+    float* d_err = reinterpret_cast<float*>(base + o_err);
+    int32_t* d_cnt = reinterpret_cast<int32_t*>(base + o_cnt);
+    uint8_t* d_st = base + o_st;
+    uint8_t* pyr = c->klt_pyr.as<uint8_t>();
+    SLAM_HIP(c, hipMemcpyAsync(d_prev_pts, prev_pts, o_next, hipMemcpyHostToDevice, s));
+    if (a.flags & SLAM_KLT_USE_INITIAL_FLOW)
+        SLAM_HIP(c, hipMemcpyAsync(d_next, next_pts, tot * 2 * sizeof(float), hipMemcpyHostToDevice, s));
+    SLAM_HIP(c, hipMemsetAsync(d_cnt, 0, (size_t)nframes * sizeof(int32_t), s));
+    prof_begin(c, 6, s);
+    SLAM_HIP(c, launch_klt_pyramid(s, d_prev, 0, prev_step, channels, 1, L, pyr));
+    SLAM_HIP(c, launch_klt_scharr(s, pyr, L, c->klt_deriv.as<int16_t>()));
+    SLAM_HIP(c, launch_klt_pyramid(s, d_frames, frame_stride, step, channels, nframes, L, pyr + L.frame_px));
+    prof_end(c, 6, s);
+    prof_begin(c, 7, s);
+    SLAM_HIP(c, launch_klt_track(s, L, pyr, c->klt_deriv.as<int16_t>(), pyr + L.frame_px, nframes, d_prev_pts, n, d_next,
+                                 d_st, d_err, d_cnt, a.win_w, a.win_h, a.max_count, a.eps2, a.flags, a.min_eig));
+    prof_end(c, 7, s);
+    if (next_pts) SLAM_HIP(c, hipMemcpyAsync(next_pts, d_next, tot * 2 * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (status) SLAM_HIP(c, hipMemcpyAsync(status, d_st, tot, hipMemcpyDeviceToHost, s));
+    if (err) SLAM_HIP(c, hipMemcpyAsync(err, d_err, tot * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (counts) SLAM_HIP(c, hipMemcpyAsync(counts, d_cnt, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    return stream_sync(c, s);
+}
+
+static int klt_point_args(slam_ctx* c, const float* prev_pts, int n, int nframes, const float* next_pts,
+                          const uint8_t* status, const float* err, int flags, bool results_optional)
+{
+    if (n < 0 || (n > 0 && !prev_pts)) return set_err(c, SLAM_E_INVALID_ARG, "klt: null points");
+    if ((long long)n * nframes > (1ll << 24) * 8) return set_err(c, SLAM_E_INVALID_ARG, "klt: more than 2^27 tracks in one call");
+    if (n == 0) return SLAM_OK;
+    const bool none = !next_pts && !status && !err;
+    if (results_optional && none && !(flags & SLAM_KLT_USE_INITIAL_FLOW)) return SLAM_OK;
+    if (!next_pts || !status || !err) return set_err(c, SLAM_E_INVALID_ARG, "klt: null result arrays");
+    return SLAM_OK;
+}
+
+int slam_klt_track(slam_ctx* c, const uint8_t* prev, size_t prev_step, const uint8_t* next, size_t next_step, int w, int h,
+                   int channels, const float* prev_pts, int n, float* next_pts, uint8_t* status, float* err, int win_w,
+                   int win_h, int max_level, int max_count, double eps, int flags, double min_eig)
+{
+    if (!c) return SLAM_E_INVALID_ARG;
+    if (int rc = async_guard(c)) return rc;
+    KltArgs a;
+    if (int rc = klt_args(c, w, h, channels, win_w, win_h, max_level, max_count, eps, flags, min_eig, &a)) return rc;
+    const size_t row = (size_t)w * channels;
+    if (!prev || !next || prev_step < row || next_step < row)
+        return set_err(c, SLAM_E_INVALID_ARG, "klt: null frame or short row stride");
+    if (int rc = klt_point_args(c, prev_pts, n, 1, next_pts, status, err, flags, false)) return rc;
+    if (n == 0) return SLAM_OK;
+    SLAM_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    SLAM_HIP(c, c->klt_img.ensure(2 * row * h));
+    uint8_t* d = c->klt_img.as<uint8_t>();
+    if (int rc = klt_upload(c, s, d, prev, prev_step, row, h)) return rc;
+    if (int rc = klt_upload(c, s, d + row * h, next, next_step, row, h)) return rc;
+    return klt_run(c, s, d, row, d + row * h, row * h, row, 1, w, h, channels, prev_pts, n, next_pts, status, err, nullptr, a);
+}
+
+int slam_klt_track_dev(slam_ctx* c, void* stream, const uint8_t* d_prev, const uint8_t* d_next, int w, int h, size_t step,
+                       int channels, const float* prev_pts, int n, float* next_pts, uint8_t* status, float* err,
+                       int win_w, int win_h, int max_level, int max_count, double eps, int flags, double min_eig)
+{
+    if (!c) return SLAM_E_INVALID_ARG;
+    KltArgs a;
+    if (int rc = klt_args(c, w, h, channels, win_w, win_h, max_level, max_count, eps, flags, min_eig, &a)) return rc;
+    if (!d_prev || !d_next || step < (size_t)w * channels)
+        return set_err(c, SLAM_E_INVALID_ARG, "klt: null frame or short row stride");
+    if (int rc = klt_point_args(c, prev_pts, n, 1, next_pts, status, err, flags, false)) return rc;
+    if (n == 0) return SLAM_OK;
+    SLAM_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    return klt_run(c, s, d_prev, step, d_next, step * h, step, 1, w, h, channels, prev_pts, n, next_pts, status, err, nullptr,
+                   a);
+}
+
+int slam_klt_track_batch_dev(slam_ctx* c, void* stream, const uint8_t* d_prev, const uint8_t* d_frames, int nframes, int w,
+                             int h, int channels, const float* prev_pts, int n, float* next_pts, uint8_t* status,
+                             float* err, int32_t* counts, int win_w, int win_h, int max_level, int max_count, double eps,
+                             int flags, double min_eig)
+{
+    if (!c) return SLAM_E_INVALID_ARG;
+    KltArgs a;
+    if (int rc = klt_args(c, w, h, channels, win_w, win_h, max_level, max_count, eps, flags, min_eig, &a)) return rc;
+    if (nframes < 0 || nframes > 65535) return set_err(c, SLAM_E_INVALID_ARG, "klt: 0..65535 candidates per call");
+    if (nframes > 0 && (!d_prev || !d_frames || !counts)) return set_err(c, SLAM_E_INVALID_ARG, "klt: null frames or counts");
+    if (int rc = klt_point_args(c, prev_pts, n, nframes, next_pts, status, err, flags, true)) return rc;
+    if (nframes == 0) return SLAM_OK;
+    if (n == 0) {
+        for (int f = 0; f < nframes; f++) counts[f] = 0;
+        return SLAM_OK;
+    }
+    SLAM_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    const size_t row = (size_t)w * channels;
+    return klt_run(c, s, d_prev, row, d_frames, row * h, row, nframes, w, h, channels, prev_pts, n, next_pts, status, err,
+                   counts, a);
 }
 
 }  // extern "C"

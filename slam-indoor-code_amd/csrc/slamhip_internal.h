@@ -41,6 +41,8 @@ constexpr int kUndistTileW = 128, kUndistTileH = 8, kUndistFrames = 8;
 // ballot per row) x 16 rows; calib_subpix: the largest half window per axis
 constexpr int kChessTileW = 64, kChessTileH = 16;
 constexpr int kSubpixMaxWin = 15;
+// klt_track (klt.hip): window 3 .. 31 per axis, at most 9 pyramid levels (maxLevel 0 .. 8)
+constexpr int kKltMinWin = 3, kKltMaxWin = 31, kKltMaxLevels = 9;
 
 struct SiftConsts {
     float gauss[16];   // 13-tap kernel of GaussianBlur(sigma = sig_diff)
@@ -291,6 +293,10 @@ struct slam_ctx {
     // chessboard calibration (calib.hip): response maps, NMS masks, candidates +
     // counts, and cornerSubPix's corners + mask factors
     slamhip::DevBuf calib_resp, calib_mask, calib_out, calib_sub;
+    // pyramidal LK tracking (klt.hip): host frames staged for slam_klt_track / _pyramid, the gray
+    // pyramids (previous frame first, then the candidates), the previous frame's derivative
+    // planes, and the points + results of one call
+    slamhip::DevBuf klt_img, klt_pyr, klt_deriv, klt_pts;
 
     bool prof_on = false;
     slamhip::ProfFamily prof[8];
@@ -505,6 +511,29 @@ bool label_chessboard(const int32_t* cand, int n, int scale, int board_w, int bo
 // calibrateCamera's optimum (calib_solve.cpp); returns a SLAM_* code
 int calibrate_camera(const float* obj, const float* img, int nviews, int npts, int size_w, int size_h, double* K,
                      double* D, double* rvecs, double* tvecs, double* rms, int* iterations);
+
+// ---- pyramidal Lucas-Kanade tracking (klt.hip) ----
+// one frame's pyramid: level l is w[l] x h[l] unpadded 8-bit pixels at pixel offset off[l];
+// frames are frame_px apart; the derivative planes (int16 x 2 per pixel) use the same offsets
+struct KltLayout {
+    int nlevels;
+    int w[kKltMaxLevels], h[kKltMaxLevels];
+    uint32_t off[kKltMaxLevels];
+    uint32_t frame_px;
+};
+// buildOpticalFlowPyramid's levels for a w x h frame: maxLevel + 1, or fewer by the window rule
+KltLayout klt_layout(int w, int h, int win_w, int win_h, int max_level);
+// gray + pyrDown levels of nframes frames (frame f at img + f * frame_stride) into pyr (nframes x L.frame_px)
+hipError_t launch_klt_pyramid(hipStream_t s, const uint8_t* img, size_t frame_stride, size_t row_stride, int channels,
+                              int nframes, const KltLayout& L, uint8_t* pyr);
+// calcScharrDeriv of every level of one frame's pyramid into deriv (L.frame_px x 2 int16)
+hipError_t launch_klt_scharr(hipStream_t s, const uint8_t* pyr, const KltLayout& L, int16_t* deriv);
+// n > 0 points of the previous frame tracked into nframes > 0 candidates; counts (nframes, zeroed
+// by the caller) receives the number of status == 1 points per candidate
+hipError_t launch_klt_track(hipStream_t s, const KltLayout& L, const uint8_t* prev_pyr, const int16_t* deriv,
+                            const uint8_t* next_pyr, int nframes, const float* prev_pts, int n, float* next_pts,
+                            uint8_t* status, float* err, int32_t* counts, int win_w, int win_h, int max_count,
+                            double eps2, int flags, float min_eig);
 
 // ---- BA (ba.hip) ----
 int ba_solve(slam_ctx* c, double* K4, int nframes, double* ext6, int npoints, double* pts3, int nobs,

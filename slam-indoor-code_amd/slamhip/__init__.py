@@ -11,7 +11,7 @@ device-resident candidate scan (slamhip.batch).
 """
 from ._lib import (DMATCH_DTYPE, EMPTY_BATCH, FRAME_NOT_FOUND, KEYPOINT_DTYPE, LOSS_ARCTAN, LOSS_CAUCHY,
                    LOSS_HUBER, LOSS_NONE, LOSS_TRIVIAL, LOSS_TUKEY, NORM_DEFAULT, NORM_HAMMING, NORM_L1, NORM_L2,
-                   ORB_BF, SIFT_BF, SIFT_FLANN, TYPE_5_8, TYPE_7_12, TYPE_9_16, SIGNATURES, SlamError, lib)
+                   ORB_BF, SIFT_BF, SIFT_FLANN, KLT_GET_MIN_EIGENVALS, KLT_USE_INITIAL_FLOW, TYPE_5_8, TYPE_7_12, TYPE_9_16, SIGNATURES, SlamError, lib)
 from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_rmse, bundle_adjust_arrays,
                   bundleAdjustment, default_context, extractDescriptor, fastExtractor, getGoodMatches,
                   estimateTransformation, reconstruct, siftDetectAndCompute, siftDetectAndComputeBatch, SiftBatch, solvePnPRansac,
@@ -22,6 +22,7 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
                   delaunay2d, delaunay2dHost, delaunayStats, delaunayPredicates, meshFilter,
                   load_calibration, undistort, undistortBatch, undistortMap, undistortPoints,
                   chessCandidates, labelChessboard, findChessboardCorners, cornerSubPix, calibrateCamera,
+                  buildOpticalFlowPyramid, calcOpticalFlowPyrLK, kltLevelSizes,
                   save_calibration)
 from .config import ConfigError, ConfigService, reference_example
 from .calibration import CalibrationError, chessboard_photos_calibration

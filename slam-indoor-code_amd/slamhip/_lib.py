@@ -38,6 +38,8 @@ KNN_MODE_L2, KNN_MODE_SQRT, KNN_MODE_L2_PACKED, KNN_MODE_HAMMING_PACKED, KNN_MOD
 (KNN_VARIANT_MFMA, KNN_VARIANT_MFMA_PK_QT2, KNN_VARIANT_MFMA_PK_QT1, KNN_VARIANT_PIPE_QT2, KNN_VARIANT_PIPE_QT1,
  KNN_VARIANT_L1) = range(1, 7)
 KNN_VARIANT_XCD = 0x100
+KLT_USE_INITIAL_FLOW, KLT_GET_MIN_EIGENVALS = 4, 8     # cv::OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS
+KLT_MAX_LEVELS = 9                                     # maxLevel 0..8
 SIFT_KERNEL_AUTO, SIFT_KERNEL_BAND,SIFT_KERNEL_TAB, SIFT_KERNEL_GENERAL, SIFT_KERNEL_COLS, SIFT_KERNEL_COLW = 0, 1, 2, 3, 4, 5
 
 # byte-identical to cv::KeyPoint / cv::DMatch
@@ -136,6 +138,11 @@ SIGNATURES = {
     "slam_corner_subpix": (_I, [_P, _P, _I, _I, _SZ, _I, _P, _I, _I, _I, _I, _I, _I, _D]),
     "slam_corner_subpix_dev": (_I, [_P, _P, _P, _I, _I, _SZ, _I, _P, _I, _I, _I, _I, _I, _I, _D]),
     "slam_calibrate_camera": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "slam_klt_pyramid": (_I, [_P, _P, _I, _I, _SZ, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
+    "slam_klt_track": (_I, [_P, _P, _SZ, _P, _SZ, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _D, _I, _D]),
+    "slam_klt_track_dev": (_I, [_P, _P, _P, _P, _I, _I, _SZ, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _D, _I, _D]),
+    "slam_klt_track_batch_dev": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _D, _I,
+                                      _D]),
 }
 
 _lib = None

@@ -888,6 +888,103 @@ def cornerSubPix(frame, corners, winSize=(11, 11), criteria=(30, 1e-4), zeroZone
     return out
 
 
+def _frame134(frame):
+    a = np.asarray(frame)
+    if a.dtype != np.uint8:
+        raise TypeError("frames are 8-bit (CV_8UC1/3/4)")
+    if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (3, 4)):
+        raise ValueError("frame must be HxW, HxWx3 (BGR) or HxWx4")
+    ch = 1 if a.ndim == 2 else a.shape[2]
+    if a.strides[1:] != ((1,) if ch == 1 else (ch, 1)) or a.strides[0] < a.shape[1] * ch:
+        a = np.ascontiguousarray(a)
+    return a, a.shape[1], a.shape[0], ch
+
+
+def kltLevelSizes(w, h, winSize, maxLevel):
+    """the (w, h) of the levels cv::buildOpticalFlowPyramid builds: level 0, then
+    halves ((w + 1) / 2, (h + 1) / 2) up to maxLevel while larger than the window"""
+    out = [(int(w), int(h))]
+    while len(out) <= maxLevel:
+        w, h = (w + 1) // 2, (h + 1) // 2
+        if w <= winSize[0] or h <= winSize[1]:
+            break
+        out.append((w, h))
+    return out
+
+
+def buildOpticalFlowPyramid(img, winSize, maxLevel, withDerivatives=True, ctx=None):
+    """cv::buildOpticalFlowPyramid(img, pyramid, winSize, maxLevel, withDerivatives)
+    on the device (slam_klt_pyramid): (nlevels, levels, derivs) with levels a list
+    of unpadded uint8 (h, w) gray levels (level 0 is the gray image; 3 / 4 channels
+    go through BGR2GRAY) and derivs the int16 (h, w, 2) {Ix, Iy} planes of
+    calcScharrDeriv per level (None without withDerivatives).  nlevels is the
+    number of levels built: maxLevel + 1, or fewer when the next level would be no
+    larger than the window."""
+    ctx = ctx or default_context()
+    c = ctx.handle
+    a, w, h, ch = _frame134(img)
+    sizes = kltLevelSizes(w, h, winSize, max(int(maxLevel), 0))
+    px = sum(x * y for x, y in sizes)
+    gray = np.empty(px, np.uint8)
+    deriv = np.empty((px, 2), np.int16) if withDerivatives else None
+    out_sizes = np.zeros((L.KLT_MAX_LEVELS, 2), np.int32)
+    nl = ctypes.c_int(0)
+    need = ctypes.c_size_t(0)
+    check(lib().slam_klt_pyramid(c, ptr(a), w, h, a.strides[0], ch, int(winSize[0]), int(winSize[1]), int(maxLevel),
+                                 ctypes.byref(nl), ptr(out_sizes), ptr(gray), ptr(deriv), px, ctypes.byref(need)), c)
+    levels, derivs, off = [], [], 0
+    for lw, lh in out_sizes[:nl.value]:
+        levels.append(gray[off:off + lw * lh].reshape(lh, lw).copy())
+        if withDerivatives:
+            derivs.append(deriv[off:off + lw * lh].reshape(lh, lw, 2).copy())
+        off += lw * lh
+    return nl.value, levels, (derivs if withDerivatives else None)
+
+
+def _klt_tail(winSize, maxLevel, criteria, flags, minEigThreshold):
+    return (int(winSize[0]), int(winSize[1]), int(maxLevel), int(criteria[0]), float(criteria[1]), int(flags),
+            float(minEigThreshold))
+
+
+def calcOpticalFlowPyrLK(prev, next, prevPts, nextPts=None, winSize=(21, 21), maxLevel=3, criteria=(30, 0.01), flags=0,
+                         minEigThreshold=1e-4, ctx=None):
+    """cv::calcOpticalFlowPyrLK(prev, next, prevPts, nextPts, status, err, winSize,
+    maxLevel, TermCriteria(COUNT + EPS, *criteria), flags, minEigThreshold) on the
+    device: (nextPts (n, 2) float32, status (n,) uint8, err (n,) float32).  prev /
+    next: two host frames of one size (slam_klt_track) or two resident torch frames
+    (h, w[, 3]) (slam_klt_track_dev).  flags: L.KLT_USE_INITIAL_FLOW (nextPts holds
+    the initial positions) | L.KLT_GET_MIN_EIGENVALS.  winSize 3..31 per axis,
+    maxLevel 0..8."""
+    ctx = ctx or default_context()
+    c = ctx.handle
+    pts = np.ascontiguousarray(np.asarray(prevPts, np.float32).reshape(-1, 2))
+    n = len(pts)
+    if int(flags) & L.KLT_USE_INITIAL_FLOW:
+        if nextPts is None or np.size(nextPts) != 2 * n:
+            raise ValueError("USE_INITIAL_FLOW: one initial position per point")
+        out = np.array(nextPts, np.float32).reshape(-1, 2).copy()
+    else:
+        out = np.zeros((n, 2), np.float32)
+    status = np.ones(n, np.uint8)
+    err = np.zeros(n, np.float32)
+    tail = _klt_tail(winSize, maxLevel, criteria, flags, minEigThreshold)
+    if not isinstance(prev, np.ndarray) and hasattr(prev, "data_ptr"):
+        fr, _, w, h, ch = _resident(prev[None])
+        nx, _, w2, h2, ch2 = _resident(next[None])
+        if (w, h, ch) != (w2, h2, ch2):
+            raise ValueError("frames of one size")
+        check(lib().slam_klt_track_dev(c, None, ctypes.c_void_p(fr.data_ptr()), ctypes.c_void_p(nx.data_ptr()), w, h,
+                                       w * ch, ch, ptr(pts), n, ptr(out), ptr(status), ptr(err), *tail), c)
+        return out, status, err
+    a, w, h, ch = _frame134(prev)
+    b, w2, h2, ch2 = _frame134(next)
+    if (w, h, ch) != (w2, h2, ch2):
+        raise ValueError("frames of one size")
+    check(lib().slam_klt_track(c, ptr(a), a.strides[0], ptr(b), b.strides[0], w, h, ch, ptr(pts), n, ptr(out),
+                               ptr(status), ptr(err), *tail), c)
+    return out, status, err
+
+
 def calibrateCamera(objectPoints, imagePoints, imageSize):
     """calibrateCamera(objectPoints, imagePoints, imageSize, K, D, R, T) with default
     flags (cameraCalibration.cpp:196), on the host in f64: the optimum of the

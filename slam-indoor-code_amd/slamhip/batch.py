@@ -76,6 +76,36 @@ class DeviceBatch:
         self.matcher, self.nframes = None, n
         return counts
 
+    def track(self, prev, frames, prev_pts, next_pts=None, win=(21, 21), max_level=3, criteria=(30, 0.01), flags=0,
+              min_eig=1e-4, counts_only=False):
+        """calcOpticalFlowPyrLK of one resident previous frame's points into every
+        resident candidate in one device pass (slam_klt_track_batch_dev).  prev:
+        (h, w[, 3]) uint8 tensor; frames: (n, h, w[, 3]).  Returns (next_pts
+        (n, npts, 2), status (n, npts), err (n, npts), counts (n,)): counts[f] is
+        candidate f's number of status == 1 points; with counts_only the three
+        arrays stay on the device and are returned as None."""
+        n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+        ch = 1 if frames.dim() == 3 else int(frames.shape[3])
+        if tuple(prev.shape) != tuple(frames.shape[1:]):
+            raise ValueError("previous frame and candidates of one size")
+        assert frames.is_contiguous() and frames.is_cuda and prev.is_contiguous() and prev.is_cuda
+        pts = np.ascontiguousarray(np.asarray(prev_pts, np.float32).reshape(-1, 2))
+        m = len(pts)
+        counts = np.zeros(n, np.int32)
+        out = status = err = None
+        if int(flags) & L.KLT_USE_INITIAL_FLOW:
+            out = np.array(next_pts, np.float32).reshape(n, m, 2).copy()
+            counts_only = False
+        elif not counts_only:
+            out = np.zeros((n, m, 2), np.float32)
+        if not counts_only:
+            status, err = np.ones((n, m), np.uint8), np.zeros((n, m), np.float32)
+        check(lib().slam_klt_track_batch_dev(self.c, self._stream(), ctypes.c_void_p(prev.data_ptr()),
+                                             ctypes.c_void_p(frames.data_ptr()), n, w, h, ch, ptr(pts), m, ptr(out),
+                                             ptr(status), ptr(err), ptr(counts), int(win[0]), int(win[1]), int(max_level),
+                                             int(criteria[0]), float(criteria[1]), int(flags), float(min_eig)), self.c)
+        return out, status, err, counts
+
     def batch_counts(self):
         """descriptor-bearing keypoints per frame of the last extract (host copy)."""
         out = np.zeros(max(self.nframes, 1), np.int32)

@@ -42,7 +42,7 @@ import numpy as np
 
 from . import _lib as L
 from ._lib import DMATCH_DTYPE, KEYPOINT_DTYPE
-from .api import (bundle_adjust_arrays, estimateTransformation, extractDescriptor,
+from .api import (bundle_adjust_arrays, calcOpticalFlowPyrLK, estimateTransformation, extractDescriptor,
                   fastExtractor, getMatcherTypeIndex, loss_from_config, matchFramesPairFeatures, reconstruct,
                   rodrigues_to_matrix, rodrigues_to_vector, solvePnPRansac)
 
@@ -93,6 +93,60 @@ def device_frames(frames):
         if all(q[1] == i0 + k for k, q in enumerate(seqs)):
             return seqs[0][0][i0:i0 + len(frames)], False
     return torch.stack([f.dev for f in frames]), True
+
+
+class KltParams:
+    """slam_main(tracker="klt"): the arguments of cv::calcOpticalFlowPyrLK every
+    search tracks with (OpenCV's defaults)."""
+
+    def __init__(self, win=(21, 21), max_level=3, criteria=(30, 0.01), min_eig=1e-4):
+        self.win = (int(win[0]), int(win[1]))
+        self.max_level = int(max_level)
+        self.criteria = (int(criteria[0]), float(criteria[1]))
+        self.min_eig = float(min_eig)
+
+
+REPLENISH_DISTANCE = 7     # a FAST keypoint joins a tracked frame's features if farther than this from every survivor
+
+
+def _xy(kps):
+    return np.stack([kps["x"], kps["y"]], 1).astype(np.float32) if len(kps) else np.zeros((0, 2), np.float32)
+
+
+def tracked_features(next_pts, status, err, fast_kps, shape):
+    """tracker="klt": a winner's features and matches from its track (host only).
+    Survivors are the points with status == 1 whose position lies in the frame
+    (0 <= x <= w - 1, 0 <= y <= h - 1: the point colours are read there).  The
+    features are the survivors in query order (pt = the tracked position; size,
+    angle, octave and class_id as FAST writes them, response 0), followed by the
+    frame's own FAST keypoints, in raster order, whose pixel is farther than
+    REPLENISH_DISTANCE (Chebyshev) from every survivor's rounded position.  The
+    matches are (queryIdx = index in the previous features, trainIdx = rank among
+    the survivors, distance = err)."""
+    h, w = int(shape[0]), int(shape[1])
+    p = np.asarray(next_pts, np.float32).reshape(-1, 2)
+    with np.errstate(invalid="ignore"):
+        ok = (np.asarray(status) == 1) & (p[:, 0] >= 0) & (p[:, 0] <= w - 1) & (p[:, 1] >= 0) & (p[:, 1] <= h - 1)
+    q = np.nonzero(ok)[0]
+    surv = np.zeros(len(q), KEYPOINT_DTYPE)
+    surv["x"], surv["y"] = p[q, 0], p[q, 1]
+    surv["size"], surv["angle"], surv["class_id"] = 7.0, -1.0, -1
+    # pixels within the distance of a survivor: a 2-D difference array of the (clipped) squares
+    d = REPLENISH_DISTANCE
+    rx, ry = np.rint(p[q, 0]).astype(np.int64), np.rint(p[q, 1]).astype(np.int64)
+    acc = np.zeros((h + 1, w + 1), np.int32)
+    x0, x1 = np.clip(rx - d, 0, w), np.clip(rx + d + 1, 0, w)
+    y0, y1 = np.clip(ry - d, 0, h), np.clip(ry + d + 1, 0, h)
+    np.add.at(acc, (y0, x0), 1)
+    np.add.at(acc, (y0, x1), -1)
+    np.add.at(acc, (y1, x0), -1)
+    np.add.at(acc, (y1, x1), 1)
+    near = acc.cumsum(0).cumsum(1)[:h, :w] > 0
+    fast_kps = np.asarray(fast_kps, KEYPOINT_DTYPE)
+    fresh = fast_kps[~near[fast_kps["y"].astype(np.int64), fast_kps["x"].astype(np.int64)]] if len(fast_kps) else fast_kps
+    matches = np.zeros(len(q), DMATCH_DTYPE)
+    matches["queryIdx"], matches["trainIdx"], matches["distance"] = q, np.arange(len(q)), np.asarray(err, np.float32)[q]
+    return np.concatenate([surv, fresh]), matches
 
 
 class GpuOps:
@@ -299,6 +353,67 @@ class GpuOps:
         del batch[:good + 1]
         return out
 
+    # ---- tracker="klt": the candidate search without descriptors -----------------
+    def track(self, prev_frame, prev_kps, frame, klt=None):
+        """calcOpticalFlowPyrLK of the previous frame's keypoint positions into
+        one frame: (next_pts, status, err); resident frames are tracked in HBM"""
+        klt = klt or KltParams()
+        a, b = getattr(prev_frame, "dev", None), getattr(frame, "dev", None)
+        if a is None or b is None:
+            a, b = _host_pixels(prev_frame), _host_pixels(frame)
+        return calcOpticalFlowPyrLK(a, b, _xy(prev_kps), None, klt.win, klt.max_level, klt.criteria, 0, klt.min_eig,
+                                    ctx=self.ctx)
+
+    def track_search(self, cond, batch, prev_frame, prev_holder):
+        """search() for tracker="klt": the previous good frame's feature positions
+        tracked into every candidate in one device pass (slam_klt_track_batch_dev;
+        with early_exit, tail-first chunks), a candidate's count being its number of
+        status == 1 points; the reference's selection on those counts; then the
+        winner's track read back and its features and matches made on the host
+        (tracked_features).  Only counts cross PCIe for the other candidates."""
+        torch = self._torch()
+        db, _ = self._batches()
+        klt = cond.tracker
+        pts = _xy(prev_holder.allExtractedFeatures)
+        n, head = len(batch), cond.skipFramesFromBatchHead
+        chunk = self.early_exit if (self.early_exit > 0 and cond.useFirstFitInBatch and len(pts) > 0) else 0
+        counts = np.full(n, -1, np.int32)
+        good, good_n = FRAME_NOT_FOUND, 0
+        hi, lo, processed = n, 0, 0
+        prev = prev_frame.dev
+        while True:
+            lo = max(head, hi - chunk, 0) if chunk else 0
+            if lo >= hi:
+                break
+            frames, stacked = device_frames([el.frame for el in batch[lo:hi]])
+            if stacked:
+                torch.cuda.current_stream().synchronize()
+            mc = db.track(prev, frames, pts, None, klt.win, klt.max_level, klt.criteria, 0, klt.min_eig,
+                          counts_only=True)[3]
+            counts[lo:hi] = mc
+            processed += hi - lo
+            for bi in range(hi - 1, max(head, lo) - 1, -1):
+                batch[bi].estimated = True
+                m = int(mc[bi - lo])
+                if m >= cond.requiredMatchedPointsCount and m >= good_n:
+                    good, good_n = bi, m
+                    if cond.useFirstFitInBatch:
+                        break
+            if not chunk or good >= 0 or lo <= head:
+                break
+            hi = lo
+        self.last_counts = counts
+        self.last_processed = processed
+        if good < 0:
+            return good, None, None, None
+        el = batch[good]
+        out, st, er, _ = db.track(prev, frames[good - lo:good - lo + 1], pts, None, klt.win, klt.max_level, klt.criteria,
+                                  0, klt.min_eig)
+        el.features, el.matches = tracked_features(out[0], st[0], er[0], el.features, el.frame.shape)
+        res = (good, el.frame, el.features, el.matches)
+        del batch[:good + 1]
+        return res
+
     # ---- the other operations (host buffers: small per-frame arrays) -----------
     def describe(self, frame, kps, matcher):
         return extractDescriptor(_host_pixels(frame), kps, matcher, ctx=self.ctx)
@@ -470,6 +585,7 @@ class Conditions:
         self.rpThreshold = float(g("RPRANSACThreshold"))
         self.rpDistance = float(g("RPDistanceThreshold"))
         self.loss, self.lossParam = loss_from_config(cfg)
+        self.tracker = None       # slam_main(tracker="klt"): the KltParams of the search
 
 
 class DeviceMedia:
@@ -840,7 +956,12 @@ def find_good_frame_from_batch(media, cond, batch, prev_frame, prev_holder, ops)
     n = len(batch)
     if n == 0:
         return EMPTY_BATCH, None, None, None
-    if getattr(ops, "search", None) is not None and _resident(prev_frame) and all(_resident(el.frame) for el in batch):
+    resident = _resident(prev_frame) and all(_resident(el.frame) for el in batch)
+    if getattr(cond, "tracker", None) is not None:
+        if getattr(ops, "track_search", None) is not None and resident:
+            return ops.track_search(cond, batch, prev_frame, prev_holder)
+        return _track_scan(cond, batch, prev_frame, prev_holder, ops)
+    if getattr(ops, "search", None) is not None and resident:
         return ops.search(cond, batch, prev_frame, prev_holder)   # GpuOps: the scan in one device pass
     # the host scan reads host pixels: a frame that lives in HBM only (DeviceMedia
     # without its host copy) cannot take this path
@@ -863,6 +984,32 @@ def find_good_frame_from_batch(media, cond, batch, prev_frame, prev_holder, ops)
         return good, None, None, None
     el = batch[good]
     out = (good, el.frame, el.features.copy(), el.matches.copy())   # cv::Mat: shared
+    del batch[:good + 1]
+    return out
+
+
+def _track_scan(cond, batch, prev_frame, prev_holder, ops):
+    """tracker="klt" on the host scan: the loop of batch.cpp:101-160 with
+    ops.track(prev_frame, prev_kps, frame, klt) in place of describe + match; a
+    candidate's count is its number of status == 1 points"""
+    for f in [prev_frame] + [el.frame for el in batch]:
+        _host_pixels(f)
+    prev_kps = prev_holder.allExtractedFeatures
+    good, good_n, track = FRAME_NOT_FOUND, 0, None
+    for bi in range(len(batch) - 1, cond.skipFramesFromBatchHead - 1, -1):
+        el = batch[bi]
+        res = ops.track(prev_frame, prev_kps, el.frame, cond.tracker)
+        el.estimated = True
+        m = int(np.asarray(res[1]).sum())
+        if m >= cond.requiredMatchedPointsCount and m >= good_n:
+            good, good_n, track = bi, m, res
+            if cond.useFirstFitInBatch:
+                break
+    if good < 0:
+        return good, None, None, None
+    el = batch[good]
+    el.features, el.matches = tracked_features(track[0], track[1], track[2], el.features, el.frame.shape)
+    out = (good, el.frame, el.features, el.matches)
     del batch[:good + 1]
     return out
 
@@ -1182,7 +1329,7 @@ def define_camera_position(old_deque, last_id, fd):
 
 
 def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK=None, undistort="frames",
-              criteria=(50, 0.01), max_residual=0.01):
+              criteria=(50, 0.01), max_residual=0.01, tracker=None, klt=None):
     """src/main.cpp:71-107 slamMain: mainCycle restarts from the last pose until
     the sequence ends, then points.txt / colors.txt.  K (3x3 float64) is
     updated in place by BA, as the reference's calibrationMatrix is.  dist: the
@@ -1200,9 +1347,23 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
     winner's matches that touch one are dropped before anything reads them.  The
     essential matrix, PnP, triangulation and BA read the undistorted
     coordinates; the point colours are read from the raw frame at the raw
-    coordinates, the same physical pixel.  Returns (GlobalData, Logs)."""
+    coordinates, the same physical pixel.
+
+    tracker="klt" (opt-in; the reference's useFeatureTracker mode) searches
+    without descriptors: the previous good frame's feature positions are tracked
+    into every candidate by cv::calcOpticalFlowPyrLK with the arguments in `klt`
+    (a KltParams; OpenCV's defaults when None), a candidate's count is its number
+    of status == 1 points, and the reference's selection runs on those counts
+    unchanged.  The winner's features are its surviving tracked positions
+    followed by its own FAST keypoints away from them, its matches the tracks
+    (tracked_features).  Everything downstream is untouched.  Not combined with
+    dist.  Returns (GlobalData, Logs)."""
     if undistort not in ("frames", "points"):
         raise ValueError('undistort: "frames" or "points"')
+    if tracker not in (None, "klt"):
+        raise ValueError('tracker: None or "klt"')
+    if tracker is not None and dist is not None:
+        raise ValueError("tracker together with dist is not supported")
     ops = ops or GpuOps()
     lens = None
     if dist is not None and np.any(np.asarray(dist, np.float64) != 0):
@@ -1211,6 +1372,8 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
         else:
             lens = PointLens(ops, K, dist, K if newK is None else newK, criteria, max_residual)
     cond = Conditions(cfg)
+    if tracker is not None:
+        cond.tracker = klt or KltParams()
     logs = Logs(out_dir if out_dir is not None else None)
     gd = GlobalData()
     old, last_id = [], -1
