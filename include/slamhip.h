@@ -659,6 +659,83 @@ int slam_klt_track_batch_dev(slam_ctx* ctx, void* stream, const uint8_t* d_prev,
                              uint8_t* status, float* err, int32_t* counts, int win_w, int win_h, int max_level,
                              int max_count, double eps, int flags, double min_eig);
 
+/* ---- JPEG decoding: cv::imread / cv::imdecode on baseline JPEG ------------------- */
+/* cv::imread(path, IMREAD_COLOR / IMREAD_GRAYSCALE) and cv::imdecode on a JPEG
+ * stream (modules/imgcodecs/src/grfmt_jpeg.cpp over libjpeg's defaults: jdhuff.c,
+ * jidctint.c jpeg_idct_islow, jdsample.c fancy upsampling, jdcolor.c), restated
+ * in 32-bit integers; the numpy restatement tests/jpeg_ref.py is the contract.
+ * The reference reads its frames and calibration photos through cv::imread
+ * (usePhotosCycle / photosPathPattern; cameraCalibration.cpp:153).
+ *
+ * Accepted: SOF0 (baseline, Huffman, 8 bit), one interleaved scan; one component,
+ * or three YCbCr components with luma sampling 1x1, 2x1 or 2x2 and both chroma
+ * 1x1; 8-bit quantisation tables; up to 4 + 4 Huffman tables; restart intervals;
+ * width and height 1 .. 16384.  Read besides: the Exif orientation (APP1, tag
+ * 0x0112) and the Adobe transform flag (APP14).
+ * SLAM_E_UNSUPPORTED: SOF1 / SOF2 and the other frame types (progressive,
+ * lossless, arithmetic coding), 12-bit precision, any other sampling, 2 or 4
+ * components, RGB-coded streams (libjpeg's rule: without JFIF, Adobe transform 0
+ * or the component ids 'R' 'G' 'B'), non-interleaved or multiple scans, 16-bit
+ * quantisation tables, larger dimensions.
+ * SLAM_E_INVALID_ARG: no SOI, a segment length past the buffer, a DHT whose counts
+ * oversubscribe the code space or exceed 256 symbols, a scan that references an
+ * undefined table, no frame header or no scan.
+ *
+ * *status (per image): 0 clean, else the entropy faults met:
+ *   1 ran out of bytes, 2 no such Huffman code, 4 a run past coefficient 63,
+ *   8 a restart marker missing or out of sequence.
+ * The restart interval (or the whole scan of a stream without DRI) that meets a
+ * fault stops and its remaining blocks stay zero (gray 128); the output of a
+ * flagged stream is the same on host and device and is not libjpeg's recovery.
+ * No stream, however corrupt, makes either decoder read or write out of bounds
+ * (tests/cpp/jpeg_fuzz_test.cpp runs the shared code under the sanitizers).
+ *
+ * Deviation: libjpeg-turbo's SIMD IDCT keeps 16-bit intermediates and so differs
+ * from its own scalar code on hostile streams (quantisation tables scaled x5 and
+ * above); the definition here is the scalar arithmetic, modulo 2^32. */
+enum slam_jpeg_sampling { SLAM_JPEG_GRAY = 0, SLAM_JPEG_444 = 0x11, SLAM_JPEG_422 = 0x21, SLAM_JPEG_420 = 0x22 };
+struct slam_jpeg_info {
+    int32_t width, height;       /* as stored (before the orientation is applied) */
+    int32_t channels;            /* 1 or 3 */
+    int32_t sampling;            /* SLAM_JPEG_* */
+    int32_t restart_interval;    /* MCUs per restart interval, 0 without DRI */
+    int32_t segments;            /* independently decodable pieces of the scan */
+    int32_t orientation;         /* Exif 1 .. 8; 1 when absent or out of range */
+};
+/* the message of the calling thread's last failing slam_jpeg_info / slam_jpeg_decode_host ("" when none) */
+const char* slam_jpeg_last_error(void);
+/* parses and validates the headers; host only */
+int slam_jpeg_info(const uint8_t* buf, size_t len, struct slam_jpeg_info* out);
+/* the whole decoder on the host (the contract of slam_jpeg_decode, as
+ * slam_delaunay_2d_host is slam_delaunay_2d's): out receives height rows of
+ * width * channels bytes, `step` bytes apart; channels 3 = BGR (IMREAD_COLOR: a
+ * gray stream gives three equal channels), 1 = gray (IMREAD_GRAYSCALE: libjpeg's
+ * luma plane of a colour stream).  The orientation is not applied. */
+int slam_jpeg_decode_host(const uint8_t* buf, size_t len, uint8_t* out, size_t step, int channels, int* status);
+/* the same with the entropy decoding, IDCT, upsampling and colour conversion on
+ * the device; buf and out are host memory; synchronous */
+int slam_jpeg_decode(slam_ctx* ctx, const uint8_t* buf, size_t len, uint8_t* out, size_t step, int channels,
+                     int* status);
+/* n streams of one size w x h (host memory) decoded into resident packed BGR
+ * frames d_frames (n x h x w x 3, device) on `stream` (NULL = the context
+ * stream).  The headers are parsed on the host thread pool, the bytes and tables
+ * uploaded once, and three kernels run over the whole batch: jpeg_huff (one lane
+ * per restart interval), jpeg_idct, jpeg_upcolor.  Sampling, tables and restart
+ * intervals may differ between the streams.  Returns SLAM_OK whenever the batch
+ * ran: status[i] (host, n) is a stream's negative SLAM_E_* when it is
+ * unsupported, invalid or of another size (its frame is zeroed), else its
+ * entropy fault bits.  Synchronous. */
+int slam_jpeg_decode_batch_dev(slam_ctx* ctx, void* stream, const uint8_t* const* bufs, const size_t* lens, int n,
+                               int w, int h, uint8_t* d_frames, int* status);
+/* the Exif orientations (1 .. 8; 1 for a stream that failed) of the n streams of the context's last
+ * slam_jpeg_decode_batch_dev, which cv::imread would apply to the decoded frames */
+int slam_jpeg_last_orientations(slam_ctx* ctx, int32_t* out, int n);
+/* timing of the context's last slam_jpeg_decode_batch_dev, in ms: 0 host parse +
+ * segment table, 1 staging + upload, 2 jpeg_huff (with the clearing of the
+ * coefficients), 3 jpeg_idct, 4 jpeg_upcolor; bytes (may be NULL): 0 compressed
+ * bytes uploaded, 1 table + segment bytes uploaded, 2 coefficient bytes, 3 frame bytes written */
+int slam_jpeg_last_timing(slam_ctx* ctx, double* ms5, uint64_t* bytes4);
+
 /* ---- options ------------------------------------------------------------------ */
 /* Per-context choices; all but SLAM_OPT_PNP_SUMS (below) never change results.  SLAM_OPT_SIFT_KERNEL picks the
  * kernel for SIFT descriptors of keypoints sharing one angle and size (FAST
@@ -674,7 +751,10 @@ int slam_klt_track_batch_dev(slam_ctx* ctx, void* stream, const uint8_t* d_prev,
  * four part-walks (the tests' way to run those paths on every keypoint).
  * Unknown option or value: SLAM_E_INVALID_ARG. */
 enum slam_option { SLAM_OPT_SIFT_KERNEL = 1, SLAM_OPT_SIFT_BAND_SPLIT = 2, SLAM_OPT_PNP_SUMS = 3,
-                   SLAM_OPT_FAST_REUSE = 4 };
+                   SLAM_OPT_FAST_REUSE = 4, SLAM_OPT_JPEG_LANES = 5 };
+/* SLAM_OPT_JPEG_LANES: how many lanes of a wave of jpeg_huff take a segment each
+ * (1 .. 64); 0 (default) = one per wave until the device's wave slots are full,
+ * then as many as the segment count needs.  Never changes results. */
 /* SLAM_OPT_FAST_REUSE: 1 = slam_batch_fast's results may be taken by the next
  * batch extraction of the same frames (see slam_batch_fast for the contract the
  * caller accepts); 0 (default) = every extraction detects. */

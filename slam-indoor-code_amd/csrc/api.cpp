@@ -421,7 +421,8 @@ void slam_destroy(slam_ctx* c)
                       &c->sd_kps, &c->sd_kpc, &c->sift_tab, &c->sift_band_buf, &c->sift_cols_buf, &c->sift_cols_park, &c->sift_colw_buf, &c->sift_split, &c->sift_split_cnt, &c->sift_deal, &c->geom, &c->cluster, &c->delaunay,
                       &c->undist_xy, &c->undist_frac, &c->undist_out, &c->undist_pts,
                       &c->calib_resp, &c->calib_mask, &c->calib_out, &c->calib_sub,
-                      &c->klt_img, &c->klt_pyr, &c->klt_deriv, &c->klt_pts};
+                      &c->klt_img, &c->klt_pyr, &c->klt_deriv, &c->klt_pts,
+                      &c->jpeg_in, &c->jpeg_coef, &c->jpeg_planes, &c->jpeg_out};
     for (DevBuf* b : bufs) b->release();
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->ev_up) (void)hipEventDestroy(c->ev_up);
@@ -433,6 +434,7 @@ void slam_destroy(slam_ctx* c)
     for (hipEvent_t e : c->ev_stage)
         if (e) (void)hipEventDestroy(e);
     if (c->h_async) (void)hipHostFree(c->h_async);
+    jpeg_release(c);
     for (auto& f : c->prof)
         for (hipEvent_t e : f.ev) (void)hipEventDestroy(e);
     if (c->ev_sync) (void)hipEventDestroy(c->ev_sync);
@@ -1842,6 +1844,10 @@ int slam_set_option(slam_ctx* c, int option, int value)
     case SLAM_OPT_FAST_REUSE:
         if (value != 0 && value != 1) return set_err(c, SLAM_E_INVALID_ARG, "SLAM_OPT_FAST_REUSE takes 0 or 1");
         c->opt_fast_reuse = value;
+        return SLAM_OK;
+    case SLAM_OPT_JPEG_LANES:
+        if (value < 0 || value > 64) return set_err(c, SLAM_E_INVALID_ARG, "SLAM_OPT_JPEG_LANES takes 0 (auto) .. 64");
+        c->opt_jpeg_lanes = value;
         return SLAM_OK;
     default:
         return set_err(c, SLAM_E_INVALID_ARG, "unknown option");

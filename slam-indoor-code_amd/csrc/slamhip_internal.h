@@ -297,6 +297,17 @@ struct slam_ctx {
     // pyramids (previous frame first, then the candidates), the previous frame's derivative
     // planes, and the points + results of one call
     slamhip::DevBuf klt_img, klt_pyr, klt_deriv, klt_pts;
+    // JPEG decoding (jpeg.hip): the uploaded descriptors + segment table + status words + compressed
+    // bytes, the coefficients, the component planes, and slam_jpeg_decode's device result
+    slamhip::DevBuf jpeg_in, jpeg_coef, jpeg_planes, jpeg_out;
+    void* h_jpeg = nullptr;               // pinned staging of jpeg_in
+    size_t h_jpeg_bytes = 0;
+    void* jpeg_host = nullptr;            // the parsed headers of the last batch, kept between calls (jpeg.hip)
+    hipEvent_t jpeg_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    double jpeg_ms[5] = {0, 0, 0, 0, 0};  // slam_jpeg_last_timing
+    uint64_t jpeg_bytes[4] = {0, 0, 0, 0};
+    bool jpeg_timed = false;
+    int opt_jpeg_lanes = 0;               // SLAM_OPT_JPEG_LANES: 0 = by the segment count
 
     bool prof_on = false;
     slamhip::ProfFamily prof[8];
@@ -534,6 +545,10 @@ hipError_t launch_klt_track(hipStream_t s, const KltLayout& L, const uint8_t* pr
                             const uint8_t* next_pyr, int nframes, const float* prev_pts, int n, float* next_pts,
                             uint8_t* status, float* err, int32_t* counts, int win_w, int win_h, int max_count,
                             double eps2, int flags, float min_eig);
+
+// ---- JPEG decoding (jpeg.hip) ----
+// frees the context's host-side JPEG state (pinned staging, parsed headers, events)
+void jpeg_release(slam_ctx* c);
 
 // ---- BA (ba.hip) ----
 int ba_solve(slam_ctx* c, double* K4, int nframes, double* ext6, int npoints, double* pts3, int nobs,

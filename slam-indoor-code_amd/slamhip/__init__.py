@@ -23,7 +23,8 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
                   load_calibration, undistort, undistortBatch, undistortMap, undistortPoints,
                   chessCandidates, labelChessboard, findChessboardCorners, cornerSubPix, calibrateCamera,
                   buildOpticalFlowPyramid, calcOpticalFlowPyrLK, kltLevelSizes,
-                  save_calibration)
+                  save_calibration,
+                  imdecode, imread, imdecode_batch, jpegInfo, jpegLastTiming, applyOrientation)
 from .config import ConfigError, ConfigService, reference_example
 from .calibration import CalibrationError, chessboard_photos_calibration
 

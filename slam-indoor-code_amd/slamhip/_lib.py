@@ -31,6 +31,7 @@ OPT_SIFT_KERNEL = 1
 OPT_SIFT_BAND_SPLIT = 2
 OPT_PNP_SUMS = 3
 OPT_FAST_REUSE = 4
+OPT_JPEG_LANES = 5
 PNP_SUMS_ORDERED, PNP_SUMS_PAIRWISE = 0, 1
 BAND_SPLIT_OFF, BAND_SPLIT_AUTO, BAND_SPLIT_ALL, BAND_SPLIT_ALL4 = 0, 1, 2, 3
 STAGE_DESC_START, STAGE_DESC_END = 0, 1     # slam_order_after_stage
@@ -40,6 +41,8 @@ KNN_MODE_L2, KNN_MODE_SQRT, KNN_MODE_L2_PACKED, KNN_MODE_HAMMING_PACKED, KNN_MOD
 KNN_VARIANT_XCD = 0x100
 KLT_USE_INITIAL_FLOW, KLT_GET_MIN_EIGENVALS = 4, 8     # cv::OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS
 KLT_MAX_LEVELS = 9                                     # maxLevel 0..8
+JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = 0, 0x11, 0x21, 0x22      # slam_jpeg_info's sampling
+JPEG_EOF, JPEG_BAD_CODE, JPEG_RUN, JPEG_RESTART = 1, 2, 4, 8       # entropy fault bits of a decode's status
 SIFT_KERNEL_AUTO, SIFT_KERNEL_BAND,SIFT_KERNEL_TAB, SIFT_KERNEL_GENERAL, SIFT_KERNEL_COLS, SIFT_KERNEL_COLW = 0, 1, 2, 3, 4, 5
 
 # byte-identical to cv::KeyPoint / cv::DMatch
@@ -55,6 +58,12 @@ class BASummary(ctypes.Structure):
                 ("num_residuals", ctypes.c_int32), ("iterations", ctypes.c_int32),
                 ("successful_steps", ctypes.c_int32), ("termination", ctypes.c_int32),
                 ("usable", ctypes.c_int32), ("total_time_in_seconds", ctypes.c_double)]
+
+
+class JpegInfo(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("channels", ctypes.c_int32),
+                ("sampling", ctypes.c_int32), ("restart_interval", ctypes.c_int32), ("segments", ctypes.c_int32),
+                ("orientation", ctypes.c_int32)]
 
 
 # exported symbols and their signatures: (restype, argtypes)
@@ -143,6 +152,13 @@ SIGNATURES = {
     "slam_klt_track_dev": (_I, [_P, _P, _P, _P, _I, _I, _SZ, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _D, _I, _D]),
     "slam_klt_track_batch_dev": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _D, _I,
                                       _D]),
+    "slam_jpeg_last_error": (ctypes.c_char_p, []),
+    "slam_jpeg_info": (_I, [_P, _SZ, _P]),
+    "slam_jpeg_decode_host": (_I, [_P, _SZ, _P, _SZ, _I, _P]),
+    "slam_jpeg_decode": (_I, [_P, _P, _SZ, _P, _SZ, _I, _P]),
+    "slam_jpeg_decode_batch_dev": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "slam_jpeg_last_orientations": (_I, [_P, _P, _I]),
+    "slam_jpeg_last_timing": (_I, [_P, _P, _P]),
 }
 
 _lib = None

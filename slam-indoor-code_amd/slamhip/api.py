@@ -1056,3 +1056,126 @@ def synth_frames_dev(w, h, first, count, seed=1234, path=SYNTH_DRIFT, ctx=None, 
     check(lib().slam_synth_sequence_dev(ctx.handle, None, w, h, first, count, ctypes.c_uint64(seed), int(path),
                                         ctypes.c_void_p(out.data_ptr()) if count else None), ctx.handle)
     return out
+
+
+# ---- JPEG decoding: cv::imread / cv::imdecode on baseline JPEG (jpeg.hip, jpeg_parse.cpp) ----
+def _jpeg_bytes(buf):
+    if isinstance(buf, (bytes, bytearray, memoryview)):
+        return np.frombuffer(buf, np.uint8)
+    a = np.ascontiguousarray(buf)
+    if a.dtype != np.uint8 or a.ndim != 1:
+        raise TypeError("a JPEG stream is bytes or a 1-D uint8 array")
+    return a
+
+
+def _jpeg_check(code, ctx=None):
+    if code != L.SLAM_OK:
+        msg = lib().slam_last_error(ctx.handle) if ctx is not None else lib().slam_jpeg_last_error()
+        raise L.SlamError(code, msg.decode() if msg else "")
+
+
+def jpegInfo(buf):
+    """slam_jpeg_info: the stream's header as a dict (width, height, channels,
+    sampling, restart_interval, segments, orientation); raises SlamError for a
+    stream the decoder does not take."""
+    a = _jpeg_bytes(buf)
+    info = L.JpegInfo()
+    _jpeg_check(lib().slam_jpeg_info(ptr(a), a.size, ctypes.byref(info)))
+    return {k: getattr(info, k) for k, _ in L.JpegInfo._fields_}
+
+
+def applyOrientation(img, orientation):
+    """cv::imread's ApplyExifOrientation on an (h, w[, c]) array, as a view: Exif
+    2 mirrors, 3 turns by 180 degrees, 4 flips, 5 .. 8 transpose and then do as 1,
+    2, 3, 4 do."""
+    o = int(orientation)
+    if o >= 5:
+        img = img.swapaxes(0, 1)
+    if o in (2, 6):
+        return img[:, ::-1]
+    if o in (3, 7):
+        return img[::-1, ::-1]
+    if o in (4, 8):
+        return img[::-1]
+    return img
+
+
+def imdecode(buf, channels=3, apply_orientation=True, ctx=None, host=False, with_status=False):
+    """cv::imdecode(buf, IMREAD_COLOR) (channels 3, BGR) or IMREAD_GRAYSCALE
+    (channels 1) of a baseline JPEG stream, decoded on the device
+    (slam_jpeg_decode); host=True runs the same arithmetic on the host
+    (slam_jpeg_decode_host, the contract; needs no GPU).  Returns the (h, w,
+    channels) uint8 array with the Exif orientation applied as cv::imread applies
+    it; with_status: also the entropy fault bits (0 for a clean stream).  Raises
+    SlamError for a stream that is invalid or outside the supported format."""
+    a = _jpeg_bytes(buf)
+    info = jpegInfo(a)
+    out = np.empty((info["height"], info["width"], channels), np.uint8)
+    st = ctypes.c_int(0)
+    if host:
+        _jpeg_check(lib().slam_jpeg_decode_host(ptr(a), a.size, ptr(out), out.strides[0], int(channels), ctypes.byref(st)))
+    else:
+        ctx = ctx or default_context()
+        _jpeg_check(lib().slam_jpeg_decode(ctx.handle, ptr(a), a.size, ptr(out), out.strides[0], int(channels),
+                                           ctypes.byref(st)), ctx)
+    if apply_orientation:
+        out = np.ascontiguousarray(applyOrientation(out, info["orientation"]))
+    return (out, st.value) if with_status else out
+
+
+def imread(path, channels=3, apply_orientation=True, ctx=None, host=False):
+    """cv::imread(path) of a JPEG file: the BGR (or gray) frame, or None for what
+    cv::imread returns empty (a file that cannot be read or is no valid JPEG).  A
+    valid stream outside the decoder's format (progressive, ...) raises SlamError."""
+    try:
+        with open(path, "rb") as f:
+            data = f.read()
+    except OSError:
+        return None
+    try:
+        return imdecode(data, channels, apply_orientation, ctx=ctx, host=host)
+    except L.SlamError as e:
+        if e.code == L.SLAM_E_INVALID_ARG:
+            return None
+        raise
+
+
+def imdecode_batch(bufs, ctx=None, out=None, size=None):
+    """slam_jpeg_decode_batch_dev: n JPEG streams of one size decoded into a
+    resident (n, h, w, 3) BGR torch tensor in one pass.  size: (w, h), by default
+    that of the first stream.  Returns (frames, status, orientations): status[i] is
+    0, the stream's entropy fault bits, or its negative SLAM_E_* (frame zeroed);
+    the orientations are not applied."""
+    import torch
+    ctx = ctx or default_context()
+    arrs = [_jpeg_bytes(b) for b in bufs]
+    n = len(arrs)
+    if n == 0:
+        raise ValueError("empty batch")
+    if size is None:
+        first = jpegInfo(arrs[0])
+        size = (first["width"], first["height"])
+    w, h = int(size[0]), int(size[1])
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+    assert out.is_contiguous() and tuple(out.shape) == (n, h, w, 3) and out.dtype == torch.uint8
+    ptrs = (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])
+    lens = (ctypes.c_size_t * n)(*[a.size for a in arrs])
+    status = np.zeros(n, np.int32)
+    orient = np.ones(n, np.int32)
+    torch.cuda.current_stream(out.device).synchronize()
+    check(lib().slam_jpeg_decode_batch_dev(ctx.handle, None, ptrs, lens, n, w, h, ctypes.c_void_p(out.data_ptr()),
+                                           ptr(status)), ctx.handle)
+    check(lib().slam_jpeg_last_orientations(ctx.handle, ptr(orient), n), ctx.handle)
+    return out, status, orient
+
+
+def jpegLastTiming(ctx=None):
+    """slam_jpeg_last_timing: ({parse, upload, huff, idct, upcolor} ms, {compressed,
+    tables, coefficients, frames} bytes) of the context's last imdecode_batch."""
+    ctx = ctx or default_context()
+    ms = np.zeros(5, np.float64)
+    nb = np.zeros(4, np.uint64)
+    check(lib().slam_jpeg_last_timing(ctx.handle, ptr(ms), ptr(nb)), ctx.handle)
+    return (dict(zip(("parse_ms", "upload_ms", "huff_ms", "idct_ms", "upcolor_ms"), ms.tolist())),
+            dict(zip(("compressed_bytes", "table_bytes", "coef_bytes", "frame_bytes"), [int(v) for v in nb])))

@@ -78,14 +78,18 @@ class DeviceOps:
 
 
 def chessboard_photos_calibration(frames_or_paths, iters_count=10, square_size=23.0, board_size=(7, 7), ops=None,
-                                  ctx=None, with_corners=False):
+                                  ctx=None, with_corners=False, decoder=None):
     """chessboardPhotosCalibration (cameraCalibration.cpp:142-203): frames (arrays or
     paths) are examined in order; empty frames and frames without a board are
     skipped; the search stops at iters_count boards; fewer than 10
     (MINIMAL_FOUND_FRAMES_COUNT) raise CalibrationError.  Returns (rms, K, D, R, T),
     with the refined corners (nviews, n, 2) appended when with_corners.
     ops: an object with detect(frames, board_size) -> [(found, refined corners)]
-    (default: DeviceOps(ctx))."""
+    (default: DeviceOps(ctx)).  decoder: None = read_frame (PIL on the host);
+    "gpu" = paths ending in .jpg / .jpeg are decoded on the device (api.imread,
+    byte-identical to cv::imread on baseline JPEG); other paths go to read_frame."""
+    if decoder not in (None, "gpu"):
+        raise ValueError("decoder is None or 'gpu'")
     ops = ops or DeviceOps(ctx)
     obj = object_points(board_size, square_size)
     image_points = []
@@ -98,7 +102,10 @@ def chessboard_photos_calibration(frames_or_paths, iters_count=10, square_size=2
         while pos < len(items) and len(frames) < iters_count - len(image_points):
             item = items[pos]
             pos += 1
-            frame = read_frame(item) if isinstance(item, (str, os.PathLike)) else item
+            if decoder == "gpu" and isinstance(item, (str, os.PathLike)) and str(item).lower().endswith((".jpg", ".jpeg")):
+                frame = api.imread(item, ctx=ctx)
+            else:
+                frame = read_frame(item) if isinstance(item, (str, os.PathLike)) else item
             if frame is None or np.asarray(frame).size == 0:
                 print("Empty frame", file=sys.stderr)
                 continue

@@ -625,6 +625,75 @@ class DeviceMedia:
         return out
 
 
+class JpegMedia:
+    """MediaSources over JPEG files (or streams in memory) decoded on the device:
+    the reference's usePhotosCycle input (cv::imread of every path that
+    photosPathPattern matches) without the host decoder.  take(n) decodes the next
+    files, max(n, chunk) of them, in one slam_jpeg_decode_batch_dev call into one
+    resident (k, h, w, 3) tensor and hands out ResidentFrames that are views of it,
+    as DeviceMedia does: the frames of a batch are one contiguous range.  The host
+    copy (the reference reads point colours from the cv::Mat) is fetched once per
+    chunk.  All streams must have one size and one Exif orientation, which is
+    applied as cv::imread applies it (torch view operations, then one packed copy);
+    a stream the decoder refuses raises SlamError, entropy faults (status bits) are
+    kept in `faults` and the frame is used as decoded."""
+
+    def __init__(self, paths_or_buffers, ops, chunk=32):
+        self._items = list(paths_or_buffers)
+        self.ops, self.chunk = ops, max(1, int(chunk))
+        self._pos = 0            # the next item to decode
+        self._seq = None         # DeviceMedia over the current chunk
+        self._size = None
+        self._orientation = None
+        self.faults = {}         # item index -> status bits
+
+    def _decode(self, n):
+        from . import api
+        items = self._items[self._pos:self._pos + n]
+        bufs = []
+        for it in items:
+            if isinstance(it, (str, os.PathLike)):
+                with open(it, "rb") as f:
+                    it = f.read()
+            bufs.append(it)
+        dev, status, orient = api.imdecode_batch(bufs, ctx=self.ops.ctx, size=self._size)
+        for k, st in enumerate(status):
+            if st < 0:
+                raise L.SlamError(int(st), f"JPEG stream {self._pos + k} cannot be decoded")
+            if st:
+                self.faults[self._pos + k] = int(st)
+        if self._size is None:
+            self._size = (dev.shape[2], dev.shape[1])
+            self._orientation = int(orient[0])
+        if any(int(o) != self._orientation for o in orient):
+            raise ValueError("JpegMedia needs one Exif orientation per sequence")
+        o = self._orientation
+        if o != 1:
+            if o >= 5:
+                dev = dev.transpose(1, 2)
+            if o in (2, 6):
+                dev = dev.flip(2)
+            elif o in (3, 7):
+                dev = dev.flip(1, 2)
+            elif o in (4, 8):
+                dev = dev.flip(1)
+            dev = dev.contiguous()
+        self._pos += len(items)
+        self._seq = DeviceMedia(dev.cpu().numpy(), dev)
+
+    def take(self, n):
+        if self._seq is None or self._seq.i >= len(self._seq.dev):
+            left = len(self._items) - self._pos
+            if left <= 0 or n <= 0:
+                return []
+            self._decode(min(left, max(n, self.chunk)))
+        return self._seq.take(n)
+
+    def next_frame(self):
+        f = self.take(1)
+        return f[0] if f else None
+
+
 class UndistortedMedia:
     """Any media with cv::undistort(frame, K, dist, newK) applied where the
     reference marks the seam (batch.cpp:244, between getNextFrame and
