@@ -736,6 +736,59 @@ int slam_jpeg_last_orientations(slam_ctx* ctx, int32_t* out, int n);
  * bytes uploaded, 1 table + segment bytes uploaded, 2 coefficient bytes, 3 frame bytes written */
 int slam_jpeg_last_timing(slam_ctx* ctx, double* ms5, uint64_t* bytes4);
 
+/* ---- scene rendering (the cv::viz window of vizualizePointsAndCameras, headless) -- */
+/* A deterministic z-buffer rasteriser for the onlyViz scene: the coloured cloud
+ * (WCloud: n_pts x 3 f32 points, n_pts x 3 u8 BGR colours), the meshes (WMesh:
+ * n_faces x 3 int32 indices into the cloud, vertex colours = the cloud's) and the
+ * trajectory (WTrajectory: n_lines x 6 f32 segments a b, n_lines x 3 u8 BGR).
+ * tests/render_ref.py is the definition and the kernels equal it byte for byte
+ * from any launch order; csrc/render_setup.h states every rounding.
+ *   view    12 f64: R (3 x 3, row major) then t of the camera-to-world pose, as
+ *           viz::Viz3d::setViewerPose takes an Affine3d.  The camera looks along
+ *           +z, x right, y down; p_cam = R^T (p - t).
+ *   cam     6 f64: fx fy cx cy near far.  u = fx X / Z + cx, v = fy Y / Z + cy,
+ *           pixel (i, j) covers [i, i + 1) x [j, j + 1).
+ *   points  a square of point_size (odd, 1 .. 7) pixels about the pixel holding
+ *           the projection, at the point's 1/Z; culled outside near <= Z <= far
+ *           or the viewport
+ *   lines   clipped, endpoints snapped to pixels, walked from the endpoint lower
+ *           in (y, x) by the midpoint rule, 1/Z affine along the major axis
+ *   faces   clipped against near, far and a guard band of 32768 pixels about the
+ *           viewport, fanned, snapped to 1/16 pixel, two-sided, int64 edge
+ *           functions with the top-left rule, exact integer Gouraud blend,
+ *           1/Z affine in screen space, rounded to f32.  No lighting.
+ * Per pixel the smallest key (~bits(f32 1/Z) << 32 | kind << 30 | index) wins,
+ * kind 0 point, 1 line, 2 face: the nearer fragment; at equal depth a point
+ * beats a line beats a face, then the lower index.  Outputs per view: d_out
+ * h x w x 3 BGR (white where nothing is drawn), d_ids (nullable) the key's low
+ * word as an int32 ((id >> 30) & 3 is the kind, id & 0x3fffffff the index, so a
+ * face's id is negative) or -1, d_depth (nullable) f32 1/Z or 0.  A primitive with a
+ * non-finite coordinate or a face index outside the cloud is skipped.
+ * views is host memory (nv x 12), everything d_* is device memory; the work
+ * runs on `stream` (NULL = the context stream) in chunks of views that fit the
+ * context's key buffer (chunk_views > 0 lowers the chunk; the result does not
+ * depend on it) and the call returns when it is done.  raster_mode: 0 = faces
+ * by bounding-box size, 1 = a thread per face, 2 = a wave per tile for every
+ * face, 3 = as 2 with a tile list of 64 entries, so that nearly every tile takes
+ * the path of a full list (same result; for tests).  w, h 1 .. 8192; fx, fy finite and non-zero;
+ * 0 < near < far; at most 2^30 primitives of a kind; else SLAM_E_INVALID_ARG
+ * and nothing is launched.  nv = 0 and no primitives (white frames) are fine. */
+int slam_render_views_dev(slam_ctx* ctx, void* stream, const float* d_pts, const uint8_t* d_colors, int n_pts,
+                          const int32_t* d_faces, int n_faces, const float* d_lines, const uint8_t* d_line_colors,
+                          int n_lines, const double* views, int nv, const double* cam, int w, int h, int point_size,
+                          uint8_t* d_out, int32_t* d_ids, float* d_depth, int chunk_views, int raster_mode);
+/* one view of host primitives into host memory (ids, depth nullable); synchronous */
+int slam_render(slam_ctx* ctx, const float* pts, const uint8_t* colors, int n_pts, const int32_t* faces, int n_faces,
+                const float* lines, const uint8_t* line_colors, int n_lines, const double* view, const double* cam, int w,
+                int h, int point_size, uint8_t* out, int32_t* ids, float* depth);
+/* the context's last rendering call, summed over its views.  stats[5]: 0 primitives
+ * in (views x primitives), 1 skipped (non-finite, bad index, or outside the
+ * fixed-point range), 2 clipped away (nothing left inside the clip volume or the
+ * viewport), 3 rasterised (points, segments and fan triangles walked), 4 fragments
+ * tested.  ms[4] (nullable), HIP events on the call's stream: 0 clear, 1 points +
+ * lines, 2 faces (set-up and both raster paths), 3 resolve. */
+int slam_render_last_stats(slam_ctx* ctx, uint64_t* stats, double* ms);
+
 /* ---- options ------------------------------------------------------------------ */
 /* Per-context choices; all but SLAM_OPT_PNP_SUMS (below) never change results.  SLAM_OPT_SIFT_KERNEL picks the
  * kernel for SIFT descriptors of keypoints sharing one angle and size (FAST

@@ -308,6 +308,14 @@ struct slam_ctx {
     uint64_t jpeg_bytes[4] = {0, 0, 0, 0};
     bool jpeg_timed = false;
     int opt_jpeg_lanes = 0;               // SLAM_OPT_JPEG_LANES: 0 = by the segment count
+    // scene rendering (render.hip): counters + per-view lists + the key buffer of one chunk of views;
+    // slam_render's staged host primitives and its device result
+    slamhip::DevBuf render_ws, render_in, render_out;
+    bool render_ran = false;              // slam_render_last_stats has a call to report
+    hipStream_t render_stream = nullptr;  // the stream of the last call
+    unsigned long long render_in_count = 0;   // views x primitives of the last call
+    std::vector<hipEvent_t> render_evs;   // five per chunk of views of the largest call so far
+    double render_ms[4] = {0, 0, 0, 0};   // clear, points + lines, triangles, resolve
 
     bool prof_on = false;
     slamhip::ProfFamily prof[8];
@@ -549,6 +557,10 @@ hipError_t launch_klt_track(hipStream_t s, const KltLayout& L, const uint8_t* pr
 // ---- JPEG decoding (jpeg.hip) ----
 // frees the context's host-side JPEG state (pinned staging, parsed headers, events)
 void jpeg_release(slam_ctx* c);
+
+// ---- scene rendering (render.hip) ----
+// destroys the context's render events
+void render_release(slam_ctx* c);
 
 // ---- BA (ba.hip) ----
 int ba_solve(slam_ctx* c, double* K4, int nframes, double* ext6, int npoints, double* pts3, int nobs,

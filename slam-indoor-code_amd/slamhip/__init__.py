@@ -24,7 +24,8 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
                   chessCandidates, labelChessboard, findChessboardCorners, cornerSubPix, calibrateCamera,
                   buildOpticalFlowPyramid, calcOpticalFlowPyrLK, kltLevelSizes,
                   save_calibration,
-                  imdecode, imread, imdecode_batch, jpegInfo, jpegLastTiming, applyOrientation)
+                  imdecode, imread, imdecode_batch, jpegInfo, jpegLastTiming, applyOrientation,
+                  renderViews, renderCamera, renderStats)
 from .config import ConfigError, ConfigService, reference_example
 from .calibration import CalibrationError, chessboard_photos_calibration
 

@@ -1179,3 +1179,109 @@ def jpegLastTiming(ctx=None):
     check(lib().slam_jpeg_last_timing(ctx.handle, ptr(ms), ptr(nb)), ctx.handle)
     return (dict(zip(("parse_ms", "upload_ms", "huff_ms", "idct_ms", "upcolor_ms"), ms.tolist())),
             dict(zip(("compressed_bytes", "table_bytes", "coef_bytes", "frame_bytes"), [int(v) for v in nb])))
+
+
+# ---- scene rendering (the cv::viz window of vizualizePointsAndCameras, headless) ----
+
+def renderCamera(size=(1000, 1000)):
+    """viz::Camera(Vec2d(1, 1), Size(w, h)) as (fx, fy, cx, cy, near, far): a field
+    of view of 1 rad per axis, f = (size / 2) / tan(0.5), the principal point at
+    the centre, and the clip range (0.01, 1000.01) viz::Camera starts with."""
+    w, h = size
+    return ((w / 2) / math.tan(0.5), (h / 2) / math.tan(0.5), w / 2, h / 2, 0.01, 1000.01)
+
+
+def _views(views):
+    """(n, 12) f64: R row major then t, from a list of (R, t) or an (n, 12) array"""
+    if isinstance(views, np.ndarray) and views.ndim == 2 and views.shape[1] == 12:
+        return np.ascontiguousarray(views, np.float64)
+    out = np.zeros((len(views), 12), np.float64)
+    for i, (R, t) in enumerate(views):
+        out[i, :9] = np.asarray(R, np.float64).reshape(9)
+        out[i, 9:] = np.asarray(t, np.float64).reshape(3)
+    return out
+
+
+def renderViews(points, colors, faces, lines, line_colors, views, camera=None, size=(1000, 1000), point_size=1,
+                ids=False, depth=False, ctx=None, chunk_views=0, raster_mode=L.RENDER_AUTO):
+    """The scene of vizualizePointsAndCameras seen from each of `views` (a list of
+    camera-to-world poses (R, t), or an (n, 12) array): points (n, 3) float32 with
+    colors (n, 3) uint8 BGR (WCloud), faces (m, 3) int32 into the points (WMesh,
+    vertex colours), lines (k, 6) float32 segments with line_colors (k, 3) uint8
+    (WTrajectory).  slam_render_views_dev has the contract; tests/render_ref.py is
+    the definition.  camera: (fx, fy, cx, cy, near, far), default renderCamera(size);
+    size: (w, h).  Returns the frames (n, h, w, 3) uint8 BGR, and with ids / depth a
+    tuple that also holds the int32 id plane (kind << 30 | index, -1 for the
+    background) and the float32 1/Z plane (0 for the background).  The primitives
+    are numpy arrays (results are numpy arrays) or resident torch tensors (results
+    are tensors on their device).  chunk_views lowers the number of views per
+    pass and raster_mode picks the triangle path (L.RENDER_THREAD / _WAVE /
+    _WAVE_FULL_LIST); neither changes a byte.  One view of numpy arrays with
+    neither of them set goes through slam_render (host buffers); everything else
+    through slam_render_views_dev."""
+    ctx = ctx or default_context()
+    c = ctx.handle
+    w, h = int(size[0]), int(size[1])
+    cam = np.ascontiguousarray(camera if camera is not None else renderCamera((w, h)), np.float64).reshape(6)
+    vw = _views(views)
+    nv = len(vw)
+    resident = not isinstance(points, np.ndarray) and hasattr(points, "data_ptr")
+    if not resident and nv == 1 and not chunk_views and raster_mode == L.RENDER_AUTO:     # slam_render takes neither
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        cols = np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+        fcs = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+        lns = np.ascontiguousarray(lines, np.float32).reshape(-1, 6)
+        lcs = np.ascontiguousarray(line_colors, np.uint8).reshape(-1, 3)
+        if len(pts) != len(cols) or len(lns) != len(lcs):
+            raise ValueError("one colour per point and per line")
+        out = np.empty((1, h, w, 3), np.uint8)
+        o_ids = np.empty((1, h, w), np.int32) if ids else None
+        o_depth = np.empty((1, h, w), np.float32) if depth else None
+        check(lib().slam_render(c, ptr(pts), ptr(cols), len(pts), ptr(fcs), len(fcs), ptr(lns), ptr(lcs), len(lns), ptr(vw),
+                                ptr(cam), w, h, int(point_size), ptr(out), ptr(o_ids), ptr(o_depth)), c)
+        res = (out,) + ((o_ids,) if ids else ()) + ((o_depth,) if depth else ())
+        return res[0] if len(res) == 1 else res
+    import torch
+    if resident:
+        dev = points.device
+    else:
+        dev = torch.device("cuda", ctx.device)
+
+    def put(a, dt, width):
+        if not (not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")):
+            a = torch.from_numpy(np.ascontiguousarray(a, dt).reshape(-1, width)).to(dev)
+        if a.dtype != getattr(torch, np.dtype(dt).name) or a.dim() != 2 or a.shape[1] != width or a.device != dev:
+            raise ValueError(f"expected a resident (n, {width}) {np.dtype(dt).name} tensor")
+        return a.contiguous()
+
+    pts, cols = put(points, np.float32, 3), put(colors, np.uint8, 3)
+    fcs = put(faces, np.int32, 3)
+    lns, lcs = put(lines, np.float32, 6), put(line_colors, np.uint8, 3)
+    if len(pts) != len(cols) or len(lns) != len(lcs):
+        raise ValueError("one colour per point and per line")
+    out = torch.empty((nv, h, w, 3), dtype=torch.uint8, device=dev)
+    o_ids = torch.empty((nv, h, w), dtype=torch.int32, device=dev) if ids else None
+    o_depth = torch.empty((nv, h, w), dtype=torch.float32, device=dev) if depth else None
+    torch.cuda.current_stream(dev).synchronize()    # the tensors' producer
+
+    def dp(t):
+        return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+    check(lib().slam_render_views_dev(c, None, dp(pts), dp(cols), len(pts), dp(fcs), len(fcs), dp(lns), dp(lcs), len(lns),
+                                      ptr(vw), nv, ptr(cam), w, h, int(point_size), dp(out), dp(o_ids), dp(o_depth),
+                                      int(chunk_views), int(raster_mode)), c)
+    res = [t for t in (out, o_ids, o_depth) if t is not None]
+    if not resident:
+        res = [t.cpu().numpy() for t in res]
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def renderStats(ctx=None):
+    """slam_render_last_stats: ({primitives, skipped, clipped, rasterised, fragments},
+    {clear, points_lines, faces, resolve} ms) of the context's last renderViews"""
+    ctx = ctx or default_context()
+    st = np.zeros(5, np.uint64)
+    ms = np.zeros(4, np.float64)
+    check(lib().slam_render_last_stats(ctx.handle, ptr(st), ptr(ms)), ctx.handle)
+    return (dict(zip(("primitives", "skipped", "clipped", "rasterised", "fragments"), [int(v) for v in st])),
+            dict(zip(("clear_ms", "points_lines_ms", "faces_ms", "resolve_ms"), ms.tolist())))

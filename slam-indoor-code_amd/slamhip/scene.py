@@ -12,15 +12,26 @@ files (src/main.cpp:55-71).
                      try / catch around it, vizualizePointsAndCameras:105-115
   write_mesh         the cloud and every face as an ASCII PLY, in place of the
                      cv::viz::WMesh widgets
+  trajectory_lines   viz::WTrajectory(path, BOTH, 0.1, green), vizualizeCameras:50-54
+  reference_view     the viewer pose of vizualizeCameras:56-57
+  fly                rotationMatrixToEulerAngles + KeyboardViz3d, :149-250
+  render             the window's picture: cloud, trajectory and meshes through
+                     api.renderViews, seen with viz::Camera(Vec2d(1, 1), Size(1000, 1000))
+  write_ppm / write_png   the frames on disk
   main               the onlyViz branch of main()
 
 The numeric steps are slamhip.api's clusterizePoints / getBestFittingPlaneByPoints
 / projectToPlane / delaunay2d (HIP kernels behind the C ABI), delaunay2dHost for
-components of a few dozen points, and meshFilter.
-The cv::viz window is out of scope.
+components of a few dozen points, meshFilter, and renderViews (a z-buffer
+rasteriser in HIP: the cv::viz window is VTK over OpenGL and cannot run on a
+headless server, so the picture is the project's own, defined by
+tests/render_ref.py; the window itself and its event loop are not built).
 """
+import math
 import os
+import struct
 import sys
+import zlib
 from collections import namedtuple
 
 import numpy as np
@@ -152,10 +163,160 @@ def write_mesh(global_points, colors, meshes, path):
             f.write(f"3 {int(t[0])} {int(t[1])} {int(t[2])}\n")
 
 
-def main(config_path):
+GREEN, RED, BLUE = (0, 255, 0), (0, 0, 255), (255, 0, 0)     # viz::Color, blue-green-red
+# Point3f centroid(-0.368855, 0.538447, 7.92543), vizualizeCameras:56: narrowed to float, then an Affine3d
+REFERENCE_VIEWER_POSITION = np.array([-0.368855, 0.538447, 7.92543], np.float32).astype(np.float64)
+SPEED_MIN, SPEED_MAX, SPEED_STEP = 0.25, 2.5, 0.25
+
+
+def trajectory_lines(rotations, positions, scale=0.1, color=GREEN):
+    """viz::WTrajectory(path, WTrajectory::BOTH, scale, color) of the poses
+    Affine3d(rotations[i], positions[i]) as (lines (k, 6) float32, colours (k, 3)
+    uint8 BGR): first the polyline between consecutive positions in `color`,
+    then per pose its three axes of length `scale` from the position along the
+    columns of the rotation, x red, y green, z blue."""
+    R = [np.asarray(r, np.float64).reshape(3, 3) for r in rotations]
+    t = [np.asarray(p, np.float64).reshape(3) for p in positions]
+    if len(R) != len(t):
+        raise ValueError("Count of rotations and translations must be equal")
+    lines, cols = [], []
+    for a, b in zip(t[:-1], t[1:]):
+        lines.append(np.concatenate([a, b]))
+        cols.append(color)
+    for r, p in zip(R, t):
+        for axis, c in enumerate((RED, GREEN, BLUE)):
+            lines.append(np.concatenate([p, p + r[:, axis] * scale]))
+            cols.append(c)
+    return (np.array(lines, np.float64).astype(np.float32).reshape(-1, 6), np.array(cols, np.uint8).reshape(-1, 3))
+
+
+def reference_view(global_data):
+    """window.setViewerPose(Affine3d(rotations[0], Mat(centroid))), vizualizeCameras:56-57"""
+    if not global_data.cameraRotations:
+        raise ValueError("reference_view needs at least one camera rotation")
+    return (np.asarray(global_data.cameraRotations[0], np.float64).reshape(3, 3).copy(), REFERENCE_VIEWER_POSITION.copy())
+
+
+def rotation_to_euler(R):
+    """rotationMatrixToEulerAngles:149-185: (bank, attitude, heading), narrowed to
+    float as its Vec3f result is"""
+    m = np.asarray(R, np.float64).reshape(3, 3)
+    if m[1, 0] > 0.998:
+        e = (0.0, math.pi / 2, math.atan2(m[0, 2], m[2, 2]))
+    elif m[1, 0] < -0.998:
+        e = (0.0, -math.pi / 2, math.atan2(m[0, 2], m[2, 2]))
+    else:
+        e = (math.atan2(-m[1, 2], m[1, 1]), math.asin(m[1, 0]), math.atan2(-m[2, 0], m[0, 0]))
+    return tuple(float(np.float32(v)) for v in e)
+
+
+def fly(view, keys, speed=0.5):
+    """KeyboardViz3d:187-250 for each character of `keys`, starting from view
+    (R, t) and the reference's global `speed`: w / s move along the heading, a / d
+    along the heading -/+ 3.14 / 2.0 (the reference's constant, not pi / 2), c and
+    space move y by +/- speed * speed, + (or =, the key code 61 the reference
+    tests) and - change the speed by 0.25 within 0.25 .. 2.5.  The translation is
+    added to the pose's (Affine3d::translate); the rotation never changes.
+    Returns the list of views after each key stroke."""
+    R = np.asarray(view[0], np.float64).reshape(3, 3).copy()
+    t = np.asarray(view[1], np.float64).reshape(3).copy()
+    out = []
+    for key in keys:
+        heading = rotation_to_euler(R)[2]
+        d = np.zeros(3)
+        if key == "w":
+            d[2], d[0] = math.cos(heading) * speed, math.sin(heading) * speed
+        elif key == "s":
+            d[2], d[0] = -math.cos(heading) * speed, -math.sin(heading) * speed
+        elif key == "a":
+            d[2], d[0] = math.cos(heading - 3.14 / 2.0) * speed, math.sin(heading - 3.14 / 2.0) * speed
+        elif key == "d":
+            d[2], d[0] = math.cos(heading + 3.14 / 2.0) * speed, math.sin(heading + 3.14 / 2.0) * speed
+        elif key == "c":
+            d[1] = speed * speed
+        elif key == " ":
+            d[1] = -speed * speed
+        elif key in "+=":
+            if speed < SPEED_MAX:
+                speed += SPEED_STEP
+        elif key == "-":
+            if speed > SPEED_MIN:
+                speed -= SPEED_STEP
+        else:
+            raise ValueError(f"fly: unknown key {key!r} (w s a d c space + -)")
+        t = t + d
+        out.append((R.copy(), t.copy()))
+    return out
+
+
+def scene_primitives(global_data, meshes):
+    """what the window shows: (points float32, colours, faces, lines, line colours).
+    If the colour count differs from the point count the cloud is green
+    (getPointCloudFromPoints:28-33)."""
+    pts = np.ascontiguousarray(global_data.spatialPoints, np.float64).astype(np.float32).reshape(-1, 3)
+    cols = np.ascontiguousarray(global_data.spatialPointsColors, np.uint8).reshape(-1, 3)
+    if len(cols) != len(pts):
+        cols = np.tile(np.array(GREEN, np.uint8), (len(pts), 1))
+    faces = [m.faces for m in meshes if m is not None and len(m.faces)]
+    faces = np.concatenate(faces).astype(np.int32) if faces else np.zeros((0, 3), np.int32)
+    lines, line_cols = trajectory_lines(global_data.cameraRotations, global_data.spatialCameraPositions)
+    return pts, cols, faces, lines, line_cols
+
+
+def render(global_data, meshes, views=None, camera=None, size=(1000, 1000), point_size=1, ids=False, depth=False,
+           ctx=None):
+    """The picture of vizualizePointsAndCameras' window from each of `views`
+    (default: the reference view): api.renderViews of scene_primitives."""
+    if views is None:
+        views = [reference_view(global_data)]
+    return api.renderViews(*scene_primitives(global_data, meshes), views, camera=camera, size=size,
+                           point_size=point_size, ids=ids, depth=depth, ctx=ctx)
+
+
+render_scene = render      # main's `render` argument hides the function there
+
+
+def _rgb(frame):
+    a = np.asarray(frame)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("a frame is (h, w, 3) uint8, blue-green-red")
+    return np.ascontiguousarray(a[:, :, ::-1])
+
+
+def write_ppm(path, frame):
+    """a BGR frame as a binary PPM (P6, red-green-blue)"""
+    rgb = _rgb(frame)
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (rgb.shape[1], rgb.shape[0]))
+        f.write(rgb.tobytes())
+
+
+def write_png(path, frame):
+    """a BGR frame as an 8-bit RGB PNG: one zlib stream, filter 0 on every row"""
+    rgb = _rgb(frame)
+    h, w = rgb.shape[:2]
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+    rows = np.concatenate([np.zeros((h, 1), np.uint8), rgb.reshape(h, w * 3)], axis=1)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n")
+        f.write(chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)))
+        f.write(chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)))
+        f.write(chunk(b"IEND", b""))
+
+
+def _write_frame(path, frame):
+    (write_ppm if path.lower().endswith(".ppm") else write_png)(path, frame)
+
+
+def main(config_path, render=None):
     """the onlyViz branch of the reference's main(): reload outputDataDir's
     result files, segment the cloud and write clusters.txt and mesh.ply next to
-    them."""
+    them.  render = "view.png" also writes the reference view there (a .ppm name
+    gives a PPM); render = ("fly_%04d.png", "wwwwaadd") writes one frame per key
+    stroke of scene.fly from the reference view.  The default writes nothing more."""
     cfg = ConfigService()
     cfg.setConfigFile(config_path)
     if not cfg.getValue("onlyViz"):
@@ -164,9 +325,20 @@ def main(config_path):
     gd = load_global_data(out_dir)
     segments = segment(gd, cfg)
     write_clusters(segments, os.path.join(out_dir, "clusters.txt"))
-    write_mesh(gd.spatialPoints, gd.spatialPointsColors, mesh(segments), os.path.join(out_dir, "mesh.ply"))
+    meshes = mesh(segments)
+    write_mesh(gd.spatialPoints, gd.spatialPointsColors, meshes, os.path.join(out_dir, "mesh.ply"))
+    if render is not None:
+        draw = render_scene
+        if isinstance(render, str):
+            _write_frame(os.path.join(out_dir, render), draw(gd, meshes)[0])
+        else:
+            pattern, keys = render
+            views = fly(reference_view(gd), keys)
+            if views:
+                for i, frame in enumerate(draw(gd, meshes, views=views)):
+                    _write_frame(os.path.join(out_dir, pattern % i), frame)
     return segments
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    main(sys.argv[1], *sys.argv[2:3])
