@@ -322,12 +322,25 @@ static int dk_roots(const double* c, int n, double* re, double* im)
     return n;
 }
 
+/* diagnostics of this thread's last orc_five_point (read-only): the degree of the
+ * polynomial in z after leading zeros were dropped and its Durand-Kerner roots;
+ * 0 if the solver returned before the root finder (singular elimination, zero polynomial) */
+static __thread int g_roots_n;
+static __thread double g_roots_re[10], g_roots_im[10];
+int orc_five_point_last_roots(double re[10], double im[10])
+{
+    memcpy(re, g_roots_re, sizeof(double) * (size_t)g_roots_n);
+    memcpy(im, g_roots_im, sizeof(double) * (size_t)g_roots_n);
+    return g_roots_n;
+}
+
 /* EMEstimatorCallback::runKernel: up to 10 E (row-major 3 x 3) from 5 normalised correspondences */
 int orc_five_point(const double* q1 /* 5 x 2 */, const double* q2, double* Es /* 10 x 9 */)
 {
     /* Q (5 x 9) rows: x1 x2, y1 x2, x2, x1 y2, y1 y2, y2, x1, y1, 1 */
     double Qt[9 * 9];
     memset(Qt, 0, sizeof(Qt));
+    g_roots_n = 0;
     double Q[5][9];
     for (int i = 0; i < 5; i++) {
         const double x1 = q1[2 * i], y1 = q1[2 * i + 1], x2 = q2[2 * i], y2 = q2[2 * i + 1];
@@ -411,6 +424,9 @@ int orc_five_point(const double* q1 /* 5 x 2 */, const double* q2, double* Es /*
     if (n == 0) return 0;
     double re[10], im[10];
     dk_roots(cdet, n, re, im);
+    g_roots_n = n;
+    memcpy(g_roots_re, re, sizeof(double) * (size_t)n);
+    memcpy(g_roots_im, im, sizeof(double) * (size_t)n);
     int count = 0;
     for (int r = 0; r < n; r++) {
         if (fabs(im[r]) > 1e-10) continue;

@@ -101,6 +101,7 @@ void orc_reconstruct(const double K[9], const double R1[9], const double t1[3],
 int   orc_ep_subsets(int count, int iters, int* idx);
 int   orc_ransac_update_iters(double p, double ep, int modelPoints, int maxIters);
 int   orc_five_point(const double* q1, const double* q2, double* Es);
+int   orc_five_point_last_roots(double re[10], double im[10]);   /* degree and roots of the last call's polynomial */
 float orc_sampson(const double E[9], double x1, double y1, double x2, double y2);
 int   orc_find_essential(const float* p1, const float* p2, int n, const double K[9], double prob,
                          double threshold, double E[9], uint8_t* mask, int* niters_used);
@@ -121,6 +122,7 @@ void  orc_epnp(int n, const double* op, const float* ip, const double K[9], doub
 float orc_pnp_error(const double R[9], const double t[3], const double K[9], const float* o, const float* m);
 int   orc_pnp_iterative(const double* op, const double* ip, int n, const double K[9], double rvec[3],
                         double tvec[3]);
+void  orc_pnp_last_lm(int out[4]);   /* iterations, rejected steps, longest rejection run, largest lambdaLg10 */
 int   orc_solve_pnp_ransac(const float* op, const float* ip, int n, const double K[9], int iterationsCount,
                            float reprojectionError, double confidence, double rvec[3], double tvec[3],
                            uint8_t* mask, int* ninliers);

@@ -612,6 +612,14 @@ static void lm_step(const double JtJ[36], const double JtErr[6], int lambdaLg10,
     for (int i = 0; i < 6; i++) param[i] = prev[i] - x[i];
 }
 
+/* diagnostics of this thread's last orc_pnp_iterative (read-only: nothing
+ * below depends on them): LM iterations, rejected steps in total (a step whose
+ * error rose, so that the damping was raised), the longest run of rejections
+ * within one iteration, and the largest lambdaLg10 reached (17: the <= 16 cap
+ * ended a run, the last rejected step was kept) */
+static __thread int g_lm_stats[4];
+void orc_pnp_last_lm(int out[4]) { memcpy(out, g_lm_stats, sizeof(g_lm_stats)); }
+
 /* cvFindExtrinsicCameraParams2(useExtrinsicGuess = 1): refines rvec / tvec in
  * place over n f64 correspondences; returns the LM iteration count */
 int orc_pnp_iterative(const double* op, const double* ip, int n, const double K[9], double rvec[3], double tvec[3])
@@ -624,6 +632,7 @@ int orc_pnp_iterative(const double* op, const double* ip, int n, const double K[
     double* J = (double*)malloc(sizeof(double) * 6 * (size_t)nerr);
     double errNorm, prevErrNorm = DBL_MAX;
     int lambdaLg10 = -3, iters = 0;
+    int rejected = 0, longest = 0, maxLg10 = lambdaLg10;
     project_jac(param, K, op, ip, n, err, J);                /* STARTED */
     for (;;) {
         /* CALC_J */
@@ -637,15 +646,22 @@ int orc_pnp_iterative(const double* op, const double* ip, int n, const double K[
         lm_step(JtJ, JtErr, lambdaLg10, prev, param);
         if (iters == 0) prevErrNorm = sqrt(norm_l2sqr(err, nerr));
         /* CHECK_ERR */
+        int run = 0;
         for (;;) {
             project_jac(param, K, op, ip, n, err, NULL);
             errNorm = sqrt(norm_l2sqr(err, nerr));
+            if (errNorm > prevErrNorm) {
+                run++;
+                rejected++;
+            }
             if (errNorm > prevErrNorm && ++lambdaLg10 <= 16) {
                 lm_step(JtJ, JtErr, lambdaLg10, prev, param);
                 continue;
             }
             break;
         }
+        if (run > longest) longest = run;
+        if (lambdaLg10 > maxLg10) maxLg10 = lambdaLg10;
         lambdaLg10 = lambdaLg10 - 1 > -16 ? lambdaLg10 - 1 : -16;
         double d[6];
         for (int k = 0; k < 6; k++) d[k] = param[k] - prev[k];
@@ -655,6 +671,7 @@ int orc_pnp_iterative(const double* op, const double* ip, int n, const double K[
         project_jac(param, K, op, ip, n, err, J);            /* CALC_J */
     }
     for (int k = 0; k < 3; k++) { rvec[k] = param[k]; tvec[k] = param[3 + k]; }
+    g_lm_stats[0] = iters; g_lm_stats[1] = rejected; g_lm_stats[2] = longest; g_lm_stats[3] = maxLg10;
     free(err);
     free(J);
     return iters;
