@@ -163,6 +163,41 @@ int slam_sift_detect(slam_ctx* ctx, const uint8_t* img, int w, int h, size_t ste
 int slam_sift_detect_batch(slam_ctx* ctx, void* stream, const uint8_t* d_frames, int nframes, int w, int h,
                            int channels, slam_keypoint* d_kps, int cap, int32_t* n_out, float* d_desc);
 
+/* Full ORB detector -- the oriented, multi-scale counterpart of slam_describe's
+ * ORB (which is cv::ORB::compute on level-0 FAST corners at angle -1):
+ * cv::ORB::create(nfeatures, scale_factor, nlevels, 31, 0, 2, score_type, 31,
+ * fast_threshold)->detectAndCompute(img, noArray(), kps, desc).  Pyramid by
+ * resize(INTER_LINEAR_EXACT) chained level to level, FAST-9/16 + border 31 +
+ * retainBest per level, Harris ranking (score_type SLAM_ORB_HARRIS_SCORE) or the
+ * FAST score (SLAM_ORB_FAST_SCORE), intensity-centroid angle, steered rBRIEF.
+ * Restated from OpenCV 4.8 from upstream knowledge; fidelity to an OpenCV build
+ * is not verified (no OpenCV where this is built): the contract is
+ * tests/orb_detect_ref.py, byte for byte.  One stated deviation: keypoints come
+ * level by level and in raster (y, x) order inside a level (OpenCV's order
+ * inside a level is whatever std::nth_element leaves).  Fixed: edgeThreshold =
+ * patchSize = 31, firstLevel 0, WTA_K 2, no mask.  nlevels 1..16, scale_factor
+ * > 1 (held as the double of the float, as OpenCV does), nfeatures >= 0,
+ * channels 1 / 3 / 4, else SLAM_E_INVALID_ARG.  *n_out = total found;
+ * SLAM_E_CAPACITY if > cap (the first cap are written).  desc (nullable):
+ * cap x 32 bytes, usable with slam_match(..., SLAM_ORB_BF). */
+enum slam_orb_score { SLAM_ORB_HARRIS_SCORE = 0, SLAM_ORB_FAST_SCORE = 1 };   /* cv::ORB::ScoreType */
+int slam_orb_detect(slam_ctx* ctx, const uint8_t* img, int w, int h, size_t step, int channels, int nfeatures,
+                    float scale_factor, int nlevels, int fast_threshold, int score_type, slam_keypoint* kps,
+                    int cap, int* n_out, uint8_t* desc);
+
+/* The same detector over a device-resident batch, with slam_sift_detect_batch's
+ * conventions: nframes packed u8 frames (channels 1, 3 or 4) in device memory,
+ * every kernel launch covers one pyramid level of the whole batch; frame f's
+ * keypoints go to d_kps[f * cap ..] and its descriptors (nullable) to
+ * d_desc[f * cap * 32 ..] (device pointers, 4-byte aligned), n_out (host) [f] = keypoints found
+ * in frame f, SLAM_E_CAPACITY if any exceeds cap.  Runs on `stream` (NULL: the
+ * context's) and returns with it drained.  At most 256 frames per call; the
+ * scratch is ~3.2 x the gray frames.  A published slam_batch_* result is
+ * released. */
+int slam_orb_detect_batch(slam_ctx* ctx, void* stream, const uint8_t* d_frames, int nframes, int w, int h,
+                          int channels, int nfeatures, float scale_factor, int nlevels, int fast_threshold,
+                          int score_type, slam_keypoint* d_kps, int cap, int32_t* n_out, uint8_t* d_desc);
+
 /* reconstruct(calibration, rotation1, transition1, rotation2, transition2,
  * points1, points2, spatialPoints) -- src/mainModule/triangulation/
  * triangulate.cpp:74-100: P_v = K [R_v | t_v], per
@@ -846,7 +881,9 @@ int slam_last_knn_launch(const slam_ctx* ctx, int* mode, int* tsplit, int* varia
 /* ---- profiling hooks (bench.py) ---------------------------------------------- */
 /* average duration (ms) of the last batch's launches of one kernel family,
  * measured with HIP events on the launch stream: 0 fast, 1 sift_desc, 2 knn,
- * 3 orb_desc, 4 sift_blur, 5 ratio/compact, 6 klt pyramids + derivatives, 7 klt_track */
+ * 3 orb_desc, 4 sift_blur, 5 ratio/compact, 6 klt pyramids + derivatives, 7 klt_track,
+ * 8 orbdet_gray + orbdet_down, 9 orbdet_select + orbdet_pack, 10 orbdet_harris + orbdet_angle,
+ * 11 orbdet_emit */
 int slam_profile_enable(slam_ctx* ctx, int on);
 int slam_profile_read(slam_ctx* ctx, int family, double* avg_ms, int* launches);
 

@@ -418,7 +418,8 @@ void slam_destroy(slam_ctx* c)
                       &c->desc_norm, &c->desc_exp, &c->query_norm, &c->knn_part, &c->match_rec, &c->match_flag,
                       &c->match_cnt, &c->match_out, &c->frames_in, &c->qbuf, &c->tbuf, &c->misc, &c->ba_obs,
                       &c->ba_par, &c->ba_jac, &c->ba_red, &c->ba_S, &c->ba_aux, &c->sd_pyr, &c->sd_cand,
-                      &c->sd_kps, &c->sd_kpc, &c->sift_tab, &c->sift_band_buf, &c->sift_cols_buf, &c->sift_cols_park, &c->sift_colw_buf, &c->sift_split, &c->sift_split_cnt, &c->sift_deal, &c->geom, &c->cluster, &c->delaunay,
+                      &c->sd_kps, &c->sd_kpc, &c->od_pyr, &c->od_tab, &c->od_kps, &c->od_list, &c->od_frame, &c->od_cnt,
+                      &c->od_ang, &c->od_out, &c->sift_tab, &c->sift_band_buf, &c->sift_cols_buf, &c->sift_cols_park, &c->sift_colw_buf, &c->sift_split, &c->sift_split_cnt, &c->sift_deal, &c->geom, &c->cluster, &c->delaunay,
                       &c->undist_xy, &c->undist_frac, &c->undist_out, &c->undist_pts,
                       &c->calib_resp, &c->calib_mask, &c->calib_out, &c->calib_sub,
                       &c->klt_img, &c->klt_pyr, &c->klt_deriv, &c->klt_pts,
@@ -705,6 +706,86 @@ int slam_sift_detect_batch(slam_ctx* c, void* stream, const uint8_t* d_frames, i
         SLAM_HIP(c, hipStreamWaitEvent(s, c->ev_order, 0));
     }
     int rc = sift_detect_batch(c, s, d_frames, nframes, w, h, channels, kps, cap, n_out, desc);
+    if (rc) return rc;
+    for (int f = 0; f < nframes; f++)
+        if (n_out[f] > cap) return set_err(c, SLAM_E_CAPACITY, "keypoint buffer too small");
+    return SLAM_OK;
+}
+
+namespace {
+// the ORB detector's parameter check shared by both entry points; SLAM_OK: run
+int orb_detect_args(slam_ctx* c, int w, int channels, int nfeatures, float scale_factor, int nlevels, int score_type)
+{
+    if (channels != 1 && channels != 3 && channels != 4) return set_err(c, SLAM_E_INVALID_ARG, "channels: 1, 3 or 4");
+    if (nlevels < 1 || nlevels > kOrbDetectMaxLevels) return set_err(c, SLAM_E_INVALID_ARG, "nlevels outside 1..16");
+    if (!(scale_factor > 1.f)) return set_err(c, SLAM_E_INVALID_ARG, "scaleFactor must be above 1");
+    if (nfeatures < 0) return set_err(c, SLAM_E_INVALID_ARG, "nfeatures below 0");
+    if (score_type != SLAM_ORB_HARRIS_SCORE && score_type != SLAM_ORB_FAST_SCORE)
+        return set_err(c, SLAM_E_INVALID_ARG, "ORB score type");
+    if (w > 4096) return set_err(c, SLAM_E_UNSUPPORTED, "width > 4096");
+    return SLAM_OK;
+}
+}  // namespace
+
+int slam_orb_detect(slam_ctx* c, const uint8_t* img, int w, int h, size_t step, int channels, int nfeatures,
+                    float scale_factor, int nlevels, int fast_threshold, int score_type, slam_keypoint* kps, int cap,
+                    int* n_out, uint8_t* desc)
+{
+    if (c && c->async.state) return async_guard(c);
+    if (!c || !n_out || cap < 0 || (cap > 0 && !kps)) return SLAM_E_INVALID_ARG;
+    *n_out = 0;
+    if (int rc = orb_detect_args(c, w, channels, nfeatures, scale_factor, nlevels, score_type)) return rc;
+    if (!img || w <= 0 || h <= 0) return SLAM_OK;
+    if (!valid_image(w, h, step, channels)) return SLAM_E_INVALID_ARG;
+    SLAM_HIP(c, hipSetDevice(c->device));
+    c->batch.unpublish();       // the detector stages through the batch buffers
+    const uint8_t* dimg;
+    size_t dstep;
+    int rc = upload_image(c, img, w, h, step, channels, &dimg, &dstep);
+    if (rc) return rc;
+    const size_t kb = (size_t)std::max(cap, 1) * sizeof(slam_keypoint);
+    SLAM_HIP(c, c->od_out.ensure(kb + (size_t)std::max(cap, 1) * kOrbDescBytes));
+    slam_keypoint* d_kps = c->od_out.as<slam_keypoint>();
+    uint8_t* d_desc = c->od_out.as<uint8_t>() + kb;       // 28 cap bytes in: 4-byte aligned
+    int32_t n = 0;
+    if ((rc = orb_detect_batch(c, c->stream, dimg, 1, w, h, channels, nfeatures, (double)scale_factor, nlevels,
+                               fast_threshold, score_type, d_kps, cap, &n, desc ? d_desc : nullptr)))
+        return rc;
+    *n_out = n;
+    const int m = std::min(n, cap);
+    if (m > 0) {
+        SLAM_HIP(c, hipMemcpy(kps, d_kps, (size_t)m * sizeof(slam_keypoint), hipMemcpyDeviceToHost));
+        if (desc) SLAM_HIP(c, hipMemcpy(desc, d_desc, (size_t)m * kOrbDescBytes, hipMemcpyDeviceToHost));
+    }
+    if (n > cap) return set_err(c, SLAM_E_CAPACITY, "keypoint buffer too small");
+    return SLAM_OK;
+}
+
+int slam_orb_detect_batch(slam_ctx* c, void* stream, const uint8_t* d_frames, int nframes, int w, int h, int channels,
+                          int nfeatures, float scale_factor, int nlevels, int fast_threshold, int score_type,
+                          slam_keypoint* kps, int cap, int32_t* n_out, uint8_t* desc)
+{
+    if (c && c->async.state) return async_guard(c);
+    if (!c || nframes < 0 || cap < 0) return SLAM_E_INVALID_ARG;
+    if (int rc = orb_detect_args(c, w, channels, nfeatures, scale_factor, nlevels, score_type)) return rc;
+    if (nframes == 0) return SLAM_OK;
+    if (!n_out || (cap > 0 && !kps)) return SLAM_E_INVALID_ARG;
+    for (int f = 0; f < nframes; f++) n_out[f] = 0;
+    if (w <= 0 || h <= 0) return SLAM_OK;
+    if (!d_frames) return SLAM_E_INVALID_ARG;
+    if (nframes > kOrbDetectMaxFrames) return set_err(c, SLAM_E_INVALID_ARG, "nframes above kOrbDetectMaxFrames");
+    SLAM_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    // as slam_sift_detect_batch: the batch buffers are the detector's scratch, and a
+    // caller stream waits for the context stream's earlier readers of them
+    c->batch.unpublish();
+    if (s != c->stream) {
+        if (!c->ev_order) SLAM_HIP(c, hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming));
+        SLAM_HIP(c, hipEventRecord(c->ev_order, c->stream));
+        SLAM_HIP(c, hipStreamWaitEvent(s, c->ev_order, 0));
+    }
+    int rc = orb_detect_batch(c, s, d_frames, nframes, w, h, channels, nfeatures, (double)scale_factor, nlevels,
+                              fast_threshold, score_type, kps, cap, n_out, desc);
     if (rc) return rc;
     for (int f = 0; f < nframes; f++)
         if (n_out[f] > cap) return set_err(c, SLAM_E_CAPACITY, "keypoint buffer too small");
@@ -1866,7 +1947,7 @@ int slam_profile_enable(slam_ctx* c, int on)
 
 int slam_profile_read(slam_ctx* c, int family, double* avg_ms, int* launches)
 {
-    if (!c || family < 0 || family >= 8 || !avg_ms || !launches) return SLAM_E_INVALID_ARG;
+    if (!c || family < 0 || family >= kProfFamilies || !avg_ms || !launches) return SLAM_E_INVALID_ARG;
     ProfFamily& f = c->prof[family];
     *avg_ms = 0;
     *launches = f.used;

@@ -306,13 +306,10 @@ bool g_pat_loaded = false;
 
 }  // namespace
 
-hipError_t launch_orb_blur(slam_ctx* c, hipStream_t s, int nframes, int w, int h)
+hipError_t launch_orb_blur_planes(slam_ctx* c, hipStream_t s, const uint8_t* src, uint8_t* dst, int nframes, int w, int h)
 {
-    hipError_t e;
-    const size_t px = (size_t)nframes * w * h;
-    if ((e = c->orbblur.ensure(px)) != hipSuccess) return e;
     BlurParams b;
-    b.gray = c->gray.as<uint8_t>(); b.tmp = nullptr; b.out = c->orbblur.as<uint8_t>();
+    b.gray = src; b.tmp = nullptr; b.out = dst;
     b.w = w; b.h = h; b.k = c->orb;
     dim3 grid((w + kOT - 1) / kOT, (h + kOT - 1) / kOT, nframes);
     prof_begin(c, 4, s);
@@ -321,26 +318,33 @@ hipError_t launch_orb_blur(slam_ctx* c, hipStream_t s, int nframes, int w, int h
     return hipGetLastError();
 }
 
-hipError_t launch_orb_desc(slam_ctx* c, hipStream_t s, int nframes, int w, int h, const float* d_kp_ab, int cap)
+hipError_t launch_orb_blur(slam_ctx* c, hipStream_t s, int nframes, int w, int h)
 {
-    (void)nframes;
+    hipError_t e;
+    const size_t px = (size_t)nframes * w * h;
+    if ((e = c->orbblur.ensure(px)) != hipSuccess) return e;
+    return launch_orb_blur_planes(c, s, c->gray.as<uint8_t>(), c->orbblur.as<uint8_t>(), nframes, w, h);
+}
+
+hipError_t launch_orb_desc_on(slam_ctx* c, hipStream_t s, const uint8_t* img, int w, int h, const slam_keypoint* kps,
+                              const int* kp_frame, const int* total, const float* d_kp_ab, int cap, uint8_t* desc,
+                              uint32_t* desc_exp)
+{
     hipError_t e;
     if (!g_pat_loaded) {
         if ((e = hipMemcpyToSymbol(HIP_SYMBOL(c_pat), slam_orb_pattern31, sizeof(slam_orb_pattern31))) != hipSuccess)
             return e;
         g_pat_loaded = true;
     }
-    if ((e = c->desc_u8.ensure((size_t)cap * 32)) != hipSuccess) return e;
-    if ((e = c->desc_exp.ensure((size_t)cap * kOrbExpBytes)) != hipSuccess) return e;
     DescParams p;
-    p.img = c->orbblur.as<uint8_t>(); p.w = w; p.h = h;
-    p.kps = c->kps.as<slam_keypoint>(); p.kp_frame = c->kp_frame.as<int>(); p.total = c->misc.as<int>();
+    p.img = img; p.w = w; p.h = h;
+    p.kps = kps; p.kp_frame = kp_frame; p.total = total;
     p.cap = cap; p.kp_ab = d_kp_ab;
     const float ang = -1.f * (float)(M_PI / 180.f);
     p.a_u = cosf(ang);
     p.b_u = sinf(ang);
-    p.desc = c->desc_u8.as<uint8_t>();
-    p.desc_exp = c->desc_exp.as<uint32_t>();
+    p.desc = desc;
+    p.desc_exp = desc_exp;
     int grid = (cap + 3) / 4;
     if (grid > 16384) grid = 16384;
     if (grid < 1) grid = 1;
@@ -348,6 +352,16 @@ hipError_t launch_orb_desc(slam_ctx* c, hipStream_t s, int nframes, int w, int h
     hipLaunchKernelGGL(orb_desc, dim3(grid), dim3(256), 0, s, p);
     prof_end(c, 3, s);
     return hipGetLastError();
+}
+
+hipError_t launch_orb_desc(slam_ctx* c, hipStream_t s, int nframes, int w, int h, const float* d_kp_ab, int cap)
+{
+    (void)nframes;
+    hipError_t e;
+    if ((e = c->desc_u8.ensure((size_t)cap * 32)) != hipSuccess) return e;
+    if ((e = c->desc_exp.ensure((size_t)cap * kOrbExpBytes)) != hipSuccess) return e;
+    return launch_orb_desc_on(c, s, c->orbblur.as<uint8_t>(), w, h, c->kps.as<slam_keypoint>(), c->kp_frame.as<int>(),
+                              c->misc.as<int>(), d_kp_ab, cap, c->desc_u8.as<uint8_t>(), c->desc_exp.as<uint32_t>());
 }
 
 hipError_t launch_orb_expand(hipStream_t s, const uint8_t* d, int n, int8_t* out)

@@ -169,6 +169,7 @@ struct SiftGradBorder {
 };
 
 // events bracketing every launch of a kernel family (bench.py roofline timing)
+constexpr int kProfFamilies = 12;   // slam_profile_read's families (include/slamhip.h)
 struct ProfFamily {
     std::vector<hipEvent_t> ev;   // pairs
     int used = 0;
@@ -203,6 +204,9 @@ namespace slamhip {
 // slam_sift_detect_batch: frames per call (the pyramid is ~0.5 GB per 1080p
 // frame; candidate / keypoint scratch is 1M entries per frame, int-indexed)
 constexpr int kSiftDetectMaxFrames = 256;
+// slam_orb_detect_batch: frames per call (levels + blurred level: ~3.2 x the gray
+// frames) and pyramid levels (cv::ORB nlevels 1..16)
+constexpr int kOrbDetectMaxFrames = 256, kOrbDetectMaxLevels = 16;
 }  // namespace slamhip
 
 struct slam_ctx {
@@ -244,6 +248,12 @@ struct slam_ctx {
 
     // full SIFT detector (siftdet.hip): Gaussian + DoG pyramid, candidates, keypoints
     slamhip::DevBuf sd_pyr, sd_cand, sd_kps, sd_kpc;   // sd_kpc: the refined keypoints, frame-major
+    // full ORB detector (orbdet.hip): level planes, resize tables, the selection's second keypoint
+    // list, the packed list + its frames, counters, angles + {cos, sin}, slam_orb_detect's device result
+    slamhip::DevBuf od_pyr, od_tab, od_kps, od_list, od_frame, od_cnt, od_ang, od_out;
+    bool od_tab_valid = false;            // od_tab holds the tables of (w, h, scale factor, levels built)
+    int od_tab_w = 0, od_tab_h = 0, od_tab_levels = 0;
+    double od_tab_scale = 0;
     // two-view geometry (geom.hip); also the staged inputs of the scene calls (cluster.hip)
     slamhip::DevBuf geom;
     // scene post-processing (cluster.hip): pair counters, then the plane fit's slots
@@ -318,7 +328,7 @@ struct slam_ctx {
     double render_ms[4] = {0, 0, 0, 0};   // clear, points + lines, triangles, resolve
 
     bool prof_on = false;
-    slamhip::ProfFamily prof[8];
+    slamhip::ProfFamily prof[slamhip::kProfFamilies];
     // slam_set_option: which SIFT descriptor kernel runs (all bit-identical)
     int opt_sift_kernel = SLAM_SIFT_KERNEL_AUTO;
     int opt_band_split = SLAM_BAND_SPLIT_AUTO;
@@ -433,6 +443,14 @@ hipError_t launch_sift_desc_cols(slam_ctx* c, hipStream_t s, int w, int h, int c
 hipError_t launch_orb_blur(slam_ctx* c, hipStream_t s, int nframes, int w, int h);
 hipError_t launch_orb_desc(slam_ctx* c, hipStream_t s, int nframes, int w, int h, const float* d_kp_ab,
                            int cap);
+// the same two kernels on caller-named planes and lists (the ORB detector's pyramid levels):
+// nframes planes of w x h at src -> dst; the keypoints' patch centres are (x, y) of kps,
+// frame kp_frame[g] of img, *total of them (clipped to cap), desc / desc_exp rows per keypoint
+hipError_t launch_orb_blur_planes(slam_ctx* c, hipStream_t s, const uint8_t* src, uint8_t* dst, int nframes, int w,
+                                  int h);
+hipError_t launch_orb_desc_on(slam_ctx* c, hipStream_t s, const uint8_t* img, int w, int h, const slam_keypoint* kps,
+                              const int* kp_frame, const int* total, const float* d_kp_ab, int cap, uint8_t* desc,
+                              uint32_t* desc_exp);
 hipError_t launch_norms_u8(hipStream_t s, const uint8_t* d, int n, int32_t* norms);
 hipError_t launch_orb_expand(hipStream_t s, const uint8_t* d, int n, int8_t* out);
 
@@ -458,6 +476,15 @@ int sift_detect_batch(slam_ctx* c, hipStream_t s, const uint8_t* d_frames, int n
 hipError_t launch_gray_batch(slam_ctx* c, hipStream_t s, const uint8_t* frames, int nframes, int w, int h, int channels);
 // host cosf / sinf of 360 - angle per keypoint (calcSIFTDescriptor's rotation)
 void sift_kp_cs(const slam_keypoint* k, int n, std::vector<float>& cs);
+
+// ---- full ORB detector (orbdet.hip) ----
+struct OrbDetLevel { float scale; int w, h, nfeatures; };
+// ORB_Impl's level scales, sizes and per-level feature counts (nlevels <= kOrbDetectMaxLevels)
+void orb_detect_geometry(int w, int h, int nfeatures, double scale_factor, int nlevels, OrbDetLevel* lv);
+// d_frames: nframes packed frames; keypoints / descriptors to device memory at f * cap, counts to the host
+int orb_detect_batch(slam_ctx* c, hipStream_t s, const uint8_t* d_frames, int nframes, int w, int h, int channels,
+                     int nfeatures, double scale_factor, int nlevels, int fast_threshold, int score_type,
+                     slam_keypoint* d_kps, int cap, int32_t* n_out, uint8_t* d_desc);
 
 // ---- two-view triangulation (geom.hip) ----
 int triangulate(slam_ctx* c, const double* K, const double* R1, const double* t1, const double* R2,

@@ -11,10 +11,11 @@ device-resident candidate scan (slamhip.batch).
 """
 from ._lib import (DMATCH_DTYPE, EMPTY_BATCH, FRAME_NOT_FOUND, KEYPOINT_DTYPE, LOSS_ARCTAN, LOSS_CAUCHY,
                    LOSS_HUBER, LOSS_NONE, LOSS_TRIVIAL, LOSS_TUKEY, NORM_DEFAULT, NORM_HAMMING, NORM_L1, NORM_L2,
-                   ORB_BF, SIFT_BF, SIFT_FLANN, KLT_GET_MIN_EIGENVALS, KLT_USE_INITIAL_FLOW, TYPE_5_8, TYPE_7_12, TYPE_9_16, SIGNATURES, SlamError, lib)
+                   ORB_BF, SIFT_BF, SIFT_FLANN, HARRIS_SCORE, FAST_SCORE, KLT_GET_MIN_EIGENVALS, KLT_USE_INITIAL_FLOW, TYPE_5_8, TYPE_7_12, TYPE_9_16, SIGNATURES, SlamError, lib)
 from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_rmse, bundle_adjust_arrays,
                   bundleAdjustment, default_context, extractDescriptor, fastExtractor, getGoodMatches,
                   estimateTransformation, reconstruct, siftDetectAndCompute, siftDetectAndComputeBatch, SiftBatch, solvePnPRansac,
+                  orbDetectAndCompute, orbDetectAndComputeBatch, OrbBatch,
                   getMatcherTypeIndex, knnMatch2, lastKnnLaunch, loss_from_config, matchFeatures, matchFramesPairFeatures,
                   rodrigues_to_matrix, rodrigues_to_vector, selectGoodFrame, synth_frames,
                   SYNTH_DRIFT, SYNTH_STEADY, synth_frames_dev,

@@ -25,6 +25,7 @@ SLAM_E_SOLVER = -7
 SIFT_BF, SIFT_FLANN, ORB_BF = 0, 1, 2
 NORM_DEFAULT, NORM_L1, NORM_L2, NORM_HAMMING = 0, 2, 4, 6
 TYPE_5_8, TYPE_7_12, TYPE_9_16 = 0, 1, 2
+HARRIS_SCORE, FAST_SCORE = 0, 1          # cv::ORB::ScoreType (slam_orb_detect's score_type)
 LOSS_NONE, LOSS_TRIVIAL, LOSS_HUBER, LOSS_CAUCHY, LOSS_ARCTAN, LOSS_TUKEY = range(6)
 EMPTY_BATCH, FRAME_NOT_FOUND = -2, -1
 OPT_SIFT_KERNEL = 1
@@ -85,6 +86,8 @@ SIGNATURES = {
     "slam_describe": (_I, [_P, _P, _I, _I, _SZ, _I, _I, _P, _P, _P]),
     "slam_sift_detect": (_I, [_P, _P, _I, _I, _SZ, _I, _P, _I, _P, _P]),
     "slam_sift_detect_batch": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "slam_orb_detect": (_I, [_P, _P, _I, _I, _SZ, _I, _I, _F, _I, _I, _I, _P, _I, _P, _P]),
+    "slam_orb_detect_batch": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _I, _P, _I, _P, _P]),
     "slam_reconstruct": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "slam_estimate_transformation": (_I, [_P, _P, _P, _I, _P, _I, _D, _D, _D, _P, _P, _P, _P, _P]),
     "slam_solve_pnp_ransac": (_I, [_P, _P, _P, _I, _P, _I, ctypes.c_float, _D, _P, _P, _P, _P, _P]),

@@ -213,6 +213,67 @@ def siftDetectAndComputeBatch(frames, ctx=None, with_descriptors=True, cap=None)
         return SiftBatch(kps, desc, cnt)
 
 
+def orbDetectAndCompute(frame, nfeatures=500, scaleFactor=1.2, nlevels=8, fastThreshold=20,
+                        scoreType=L.HARRIS_SCORE, ctx=None, with_descriptors=True, cap=None):
+    """cv::ORB::create(nfeatures, scaleFactor, nlevels, 31, 0, 2, scoreType, 31,
+    fastThreshold)->detectAndCompute(frame, noArray(), kps, desc): the full ORB
+    detector (8-level pyramid, FAST + Harris ranking, intensity-centroid angle,
+    steered rBRIEF).  Returns (kps, desc); desc is n x 32 uint8, usable with
+    matchFeatures / slamhip.match(..., ORB_BF).  Keypoints come level by level,
+    raster order inside a level (slam_orb_detect).  cap: the first output
+    capacity tried (grown to the count found)."""
+    c = _ctx(ctx)
+    img, w, h, ch = _img(frame)
+    cap = int(cap) if cap is not None else max(1024, 2 * int(nfeatures) + 256)
+    while True:
+        kps = np.empty(max(cap, 1), KEYPOINT_DTYPE)
+        desc = np.empty((max(cap, 1), 32), np.uint8) if with_descriptors else None
+        n = ctypes.c_int(0)
+        rc = lib().slam_orb_detect(c, ptr(img), w, h, img.strides[0], ch, int(nfeatures), float(scaleFactor),
+                                   int(nlevels), int(fastThreshold), int(scoreType), ptr(kps), cap, ctypes.byref(n),
+                                   ptr(desc) if desc is not None else None)
+        if rc == L.SLAM_E_CAPACITY and n.value > cap:
+            cap = n.value
+            continue
+        check(rc, c)
+        return kps[:n.value].copy(), (desc[:n.value].copy() if desc is not None else None)
+
+
+class OrbBatch(SiftBatch):
+    """orbDetectAndComputeBatch's result: SiftBatch with (n, cap, 32) uint8 descriptors"""
+
+
+def orbDetectAndComputeBatch(frames, nfeatures=500, scaleFactor=1.2, nlevels=8, fastThreshold=20,
+                             scoreType=L.HARRIS_SCORE, ctx=None, with_descriptors=True, cap=None):
+    """orbDetectAndCompute over a device-resident batch: frames is a CUDA uint8
+    tensor (n, h, w, 3 or 4) or (n, h, w) already in HBM (slam_orb_detect_batch;
+    every kernel launch covers one pyramid level of the batch).  Keypoints and
+    descriptors stay in device memory: returns an OrbBatch (OrbBatch.host(f)
+    gives frame f's (kps, desc) as orbDetectAndCompute returns them)."""
+    import torch
+    c = _ctx(ctx)
+    if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() in (3, 4)):
+        raise ValueError("frames: a CUDA uint8 tensor (n, h, w[, 3 or 4])")
+    frames = frames.contiguous()
+    n, h, w = frames.shape[:3]
+    ch = frames.shape[3] if frames.dim() == 4 else 1
+    torch.cuda.current_stream(frames.device).synchronize()   # the library's stream reads the frames next
+    cap = int(cap) if cap is not None else max(1024, 2 * int(nfeatures) + 256)
+    while True:
+        kps = torch.empty((n, cap, KEYPOINT_DTYPE.itemsize), dtype=torch.uint8, device=frames.device)
+        desc = torch.empty((n, cap, 32), dtype=torch.uint8, device=frames.device) if with_descriptors else None
+        cnt = np.zeros(n, np.int32)
+        rc = lib().slam_orb_detect_batch(c, None, ctypes.c_void_p(frames.data_ptr()), n, w, h, ch, int(nfeatures),
+                                         float(scaleFactor), int(nlevels), int(fastThreshold), int(scoreType),
+                                         ctypes.c_void_p(kps.data_ptr()), cap, ptr(cnt),
+                                         ctypes.c_void_p(desc.data_ptr()) if desc is not None else None)
+        if rc == L.SLAM_E_CAPACITY and n and int(cnt.max()) > cap:
+            cap = int(cnt.max())
+            continue
+        check(rc, c)
+        return OrbBatch(kps, desc, cnt)
+
+
 def reconstruct(calibration, rotation1, transition1, rotation2, transition2, points1, points2, ctx=None):
     """triangulate.cpp:74-100 reconstruct(): DLT triangulation of matched
     points (Point2f, n x 2) seen from two cameras [R | t] with intrinsics K.
