@@ -577,6 +577,43 @@ int slam_undistort_points_dev(slam_ctx* ctx, void* stream, const float* d_src, s
                               const double* K, const double* dist, int ndist, const double* P, int max_iter,
                               double eps, float* d_dst, float* d_err);
 
+/* ---- the fisheye lens model ------------------------------------------------------ */
+/* cv::fisheye of OpenCV 4.8 with the skew fixed at 0 (DESIGN.md section 19;
+ * tests/fisheye_ref.py defines every value): theta = atan(r), theta_d = theta (1 +
+ * k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8), in uncontracted f64 with the
+ * library's own atan and tan (csrc/fisheye_math.h).  The five entry points mirror
+ * the five above argument for argument; dist is exactly ndist = 4 finite doubles
+ * k1 k2 k3 k4 (anything else: SLAM_E_INVALID_ARG).  The model is opt-in: nothing
+ * above changes, and a 4-coefficient dist means k1 k2 p1 p2 there.
+ *
+ * Frames: fisheye::undistortImage(src, dst, K, D, newK), i.e. the fixed-point
+ * map of fisheye::initUndistortRectifyMap(K, D, I, newK, size, CV_16SC2) and
+ * remap(INTER_LINEAR, BORDER_CONSTANT 0).  The map is built in one piece (no
+ * stripes), with the closed-form inverse of newK; a newK (K when NULL) whose
+ * last row is not (0, 0, 1), or a singular one: SLAM_E_INVALID_ARG.  It shares
+ * the context's map cache, keyed by the model too. */
+int slam_fisheye_undistort_batch(slam_ctx* ctx, void* stream, const uint8_t* d_src, uint8_t* d_dst, int nframes, int w,
+                                 int h, int channels, const double* K, const double* dist, int ndist,
+                                 const double* newK);
+int slam_fisheye_undistort(slam_ctx* ctx, const uint8_t* img, int w, int h, size_t step, int channels, const double* K,
+                           const double* dist, int ndist, const double* newK, uint8_t* out, size_t out_step);
+int slam_fisheye_undistort_map(slam_ctx* ctx, int w, int h, const double* K, const double* dist, int ndist,
+                               const double* newK, int16_t* xy, uint16_t* frac);
+/* fisheye::undistortPoints(src, dst, K, D, noArray(), P, criteria): Newton on
+ * theta from theta_d = |(p - c) / f| clamped to pi/2, for theta_d > 1e-8 (scale 1
+ * below).  Criteria as slam_undistort_points (OpenCV's default is 10, 1e-8): eps
+ * == 0 iterates max_iter times, eps > 0 also stops once |step| < eps.  A point
+ * that did not converge under an eps criterion, or whose theta changed sign, is
+ * (-1000000, -1000000), as OpenCV writes it, and its err is NaN; err is
+ * otherwise the distance in pixels between the input point and the forward
+ * model of the result. */
+int slam_fisheye_undistort_points(slam_ctx* ctx, const float* src, size_t src_stride, int n, const double* K,
+                                  const double* dist, int ndist, const double* P, int max_iter, double eps,
+                                  float* dst, float* err);
+int slam_fisheye_undistort_points_dev(slam_ctx* ctx, void* stream, const float* d_src, size_t src_stride, int n,
+                                      const double* K, const double* dist, int ndist, const double* P, int max_iter,
+                                      double eps, float* d_dst, float* d_err);
+
 /* ---- chessboard calibration ------------------------------------------------------ */
 /* The reference's "calibrate" mode (cameraCalibration.cpp:142-203):
  * findChessboardCorners -> cornerSubPix -> calibrateCamera.  The detector is this
@@ -603,6 +640,18 @@ int slam_chess_candidates_dev(slam_ctx* ctx, void* stream, const uint8_t* d_fram
  * least x + y (ties: least y).  *found = 0 when they are no complete board. */
 int slam_label_chessboard(const int32_t* cand, int n, int scale, int board_w, int board_h, float* corners,
                           int* found);
+/* Host only, no device: the labeller for boards that a lens bends (DESIGN.md
+ * section 19; tests/fisheye_ref.py label_board_grow defines it).  Among the 2 *
+ * board_w * board_h strongest candidates a lattice is grown breadth-first from a
+ * seed, each new node predicted from its two predecessors and taken when a
+ * candidate lies within 0.3 of the local step; the complete board_w x board_h
+ * window with the largest response sum that bends smoothly is returned in the
+ * order slam_label_chessboard uses.  At most board_w * board_h + 9 seeds are
+ * tried.  Integer exact: boards of at most 256 corners and coordinates within
+ * +-8192 (level coordinates are below 1024), so that every product of the
+ * labeller stays below 2^60 (SLAM_E_INVALID_ARG beyond). */
+int slam_label_chessboard_grow(const int32_t* cand, int n, int scale, int board_w, int board_h, float* corners,
+                               int* found);
 /* findChessboardCorners(gray, Size(board_w, board_h), corners) of a host frame:
  * slam_chess_candidates, then slam_label_chessboard. */
 int slam_find_chessboard(slam_ctx* ctx, const uint8_t* img, int w, int h, size_t step, int channels, int board_w,
@@ -633,6 +682,14 @@ int slam_corner_subpix_dev(slam_ctx* ctx, void* stream, const uint8_t* d_img, in
  * that give no homography or focal length: SLAM_E_SOLVER. */
 int slam_calibrate_camera(const float* obj, const float* img, int nviews, int npts, int size_w, int size_h,
                           double* K, double* D, double* rvecs, double* tvecs, double* rms, int* iterations);
+/* Host only, f64: the same for the fisheye lens model, the optimum of
+ * cv::fisheye::calibrate's model with the skew fixed at 0 (flags = 0 would
+ * estimate it): fx fy cx cy, k1 k2 k3 k4 and a pose per view.  D: 4 doubles.
+ * Initial values as OpenCV's: f = max(size_w, size_h) / pi, the principal point
+ * at the centre, poses from the homographies of the points undistorted with D =
+ * 0.  Arguments, *rms and the status codes as slam_calibrate_camera. */
+int slam_fisheye_calibrate(const float* obj, const float* img, int nviews, int npts, int size_w, int size_h,
+                           double* K, double* D, double* rvecs, double* tvecs, double* rms, int* iterations);
 
 /* ---- pyramidal Lucas-Kanade tracking ------------------------------------------------ */
 /* The reference's second front-end mode (README.md:173 "useFeatureTracker",

@@ -1280,10 +1280,19 @@ int slam_batch_finish(slam_ctx* c, int32_t* kp_counts, int32_t* match_counts)
     return SLAM_OK;
 }
 
-// ---- cv::undistort at the batch.cpp:244 seam (undistort.hip) ----
+// ---- cv::undistort at the batch.cpp:244 seam (undistort.hip), and the same
+// entry points for the fisheye lens model (fisheye.hip): one body per entry,
+// the model chooses the map builder and the points kernel ----
 
-int slam_undistort_batch(slam_ctx* c, void* stream, const uint8_t* d_src, uint8_t* d_dst, int nframes, int w, int h,
-                         int channels, const double* K, const double* dist, int ndist, const double* newK)
+static int lens_prepare(slam_ctx* c, hipStream_t s, int w, int h, const double* K, const double* dist, int ndist,
+                        const double* newK, int model)
+{
+    return model == kLensFisheye ? fisheye_prepare(c, s, w, h, K, dist, ndist, newK)
+                                 : undist_prepare(c, s, w, h, K, dist, ndist, newK);
+}
+
+static int undistort_batch(slam_ctx* c, void* stream, const uint8_t* d_src, uint8_t* d_dst, int nframes, int w, int h,
+                           int channels, const double* K, const double* dist, int ndist, const double* newK, int model)
 {
     if (!c) return SLAM_E_INVALID_ARG;
     if (nframes < 0 || (channels != 1 && channels != 3))
@@ -1292,7 +1301,7 @@ int slam_undistort_batch(slam_ctx* c, void* stream, const uint8_t* d_src, uint8_
     if (nframes == 0) return SLAM_OK;   // nothing to do: no map build, no launch
     SLAM_HIP(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (int rc = undist_prepare(c, s, w, h, K, dist, ndist, newK)) return rc;
+    if (int rc = lens_prepare(c, s, w, h, K, dist, ndist, newK, model)) return rc;
     if (!d_src || !d_dst) return set_err(c, SLAM_E_INVALID_ARG, "undistort: null frames");
     const size_t bytes = (size_t)w * h * channels * nframes;
     const uintptr_t a = reinterpret_cast<uintptr_t>(d_src), b = reinterpret_cast<uintptr_t>(d_dst);
@@ -1302,8 +1311,8 @@ int slam_undistort_batch(slam_ctx* c, void* stream, const uint8_t* d_src, uint8_
     return undist_mark(c, s);
 }
 
-int slam_undistort(slam_ctx* c, const uint8_t* img, int w, int h, size_t step, int channels, const double* K,
-                   const double* dist, int ndist, const double* newK, uint8_t* out, size_t out_step)
+static int undistort_frame(slam_ctx* c, const uint8_t* img, int w, int h, size_t step, int channels, const double* K,
+                           const double* dist, int ndist, const double* newK, uint8_t* out, size_t out_step, int model)
 {
     if (!c) return SLAM_E_INVALID_ARG;
     if (int rc = async_guard(c)) return rc;
@@ -1311,7 +1320,7 @@ int slam_undistort(slam_ctx* c, const uint8_t* img, int w, int h, size_t step, i
         out_step < (size_t)w * channels)
         return set_err(c, SLAM_E_INVALID_ARG, "undistort: an 8-bit image with 1 or 3 channels and an output of its size");
     SLAM_HIP(c, hipSetDevice(c->device));
-    if (int rc = undist_prepare(c, c->stream, w, h, K, dist, ndist, newK)) return rc;
+    if (int rc = lens_prepare(c, c->stream, w, h, K, dist, ndist, newK, model)) return rc;
     const uint8_t* dimg = nullptr;
     size_t dstep = 0;
     if (int rc = upload_image(c, img, w, h, step, channels, &dimg, &dstep)) return rc;
@@ -1323,13 +1332,13 @@ int slam_undistort(slam_ctx* c, const uint8_t* img, int w, int h, size_t step, i
     return stream_sync(c, c->stream);
 }
 
-int slam_undistort_map(slam_ctx* c, int w, int h, const double* K, const double* dist, int ndist, const double* newK,
-                       int16_t* xy, uint16_t* frac)
+static int undistort_map(slam_ctx* c, int w, int h, const double* K, const double* dist, int ndist, const double* newK,
+                         int16_t* xy, uint16_t* frac, int model)
 {
     if (!c) return SLAM_E_INVALID_ARG;
     if (!xy || !frac) return set_err(c, SLAM_E_INVALID_ARG, "undistort: null map output");
     SLAM_HIP(c, hipSetDevice(c->device));
-    if (int rc = undist_prepare(c, c->stream, w, h, K, dist, ndist, newK)) return rc;
+    if (int rc = lens_prepare(c, c->stream, w, h, K, dist, ndist, newK, model)) return rc;
     const size_t n = (size_t)w * h;
     SLAM_HIP(c, hipMemcpyAsync(xy, c->undist_xy.p, n * 2 * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
     SLAM_HIP(c, hipMemcpyAsync(frac, c->undist_frac.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
@@ -1337,7 +1346,65 @@ int slam_undistort_map(slam_ctx* c, int w, int h, const double* K, const double*
     return stream_sync(c, c->stream);
 }
 
+int slam_undistort_batch(slam_ctx* c, void* stream, const uint8_t* d_src, uint8_t* d_dst, int nframes, int w, int h,
+                         int channels, const double* K, const double* dist, int ndist, const double* newK)
+{
+    return undistort_batch(c, stream, d_src, d_dst, nframes, w, h, channels, K, dist, ndist, newK, kLensBrown);
+}
+
+int slam_undistort(slam_ctx* c, const uint8_t* img, int w, int h, size_t step, int channels, const double* K,
+                   const double* dist, int ndist, const double* newK, uint8_t* out, size_t out_step)
+{
+    return undistort_frame(c, img, w, h, step, channels, K, dist, ndist, newK, out, out_step, kLensBrown);
+}
+
+int slam_undistort_map(slam_ctx* c, int w, int h, const double* K, const double* dist, int ndist, const double* newK,
+                       int16_t* xy, uint16_t* frac)
+{
+    return undistort_map(c, w, h, K, dist, ndist, newK, xy, frac, kLensBrown);
+}
+
+int slam_fisheye_undistort_batch(slam_ctx* c, void* stream, const uint8_t* d_src, uint8_t* d_dst, int nframes, int w,
+                                 int h, int channels, const double* K, const double* dist, int ndist, const double* newK)
+{
+    return undistort_batch(c, stream, d_src, d_dst, nframes, w, h, channels, K, dist, ndist, newK, kLensFisheye);
+}
+
+int slam_fisheye_undistort(slam_ctx* c, const uint8_t* img, int w, int h, size_t step, int channels, const double* K,
+                           const double* dist, int ndist, const double* newK, uint8_t* out, size_t out_step)
+{
+    return undistort_frame(c, img, w, h, step, channels, K, dist, ndist, newK, out, out_step, kLensFisheye);
+}
+
+int slam_fisheye_undistort_map(slam_ctx* c, int w, int h, const double* K, const double* dist, int ndist,
+                               const double* newK, int16_t* xy, uint16_t* frac)
+{
+    return undistort_map(c, w, h, K, dist, ndist, newK, xy, frac, kLensFisheye);
+}
+
 // ---- cv::undistortPoints for the keypoints that reach geometry (undistort.hip) ----
+
+// the validated arguments of either points kernel
+struct LensPointsParams {
+    int model;
+    UndistPointsParams brown;
+    FisheyePointsParams fisheye;
+};
+
+static int lens_points_params(slam_ctx* c, const double* K, const double* dist, int ndist, const double* P, int max_iter,
+                              double eps, int model, LensPointsParams* out)
+{
+    out->model = model;
+    return model == kLensFisheye ? fisheye_points_params(c, K, dist, ndist, P, max_iter, eps, &out->fisheye)
+                                 : undist_points_params(c, K, dist, ndist, P, max_iter, eps, &out->brown);
+}
+
+static hipError_t launch_lens_points(hipStream_t s, const LensPointsParams& P, const float* src, size_t src_stride, int n,
+                                     float* dst, float* err)
+{
+    return P.model == kLensFisheye ? launch_fisheye_points(s, P.fisheye, src, src_stride, n, dst, err)
+                                   : launch_undist_points(s, P.brown, src, src_stride, n, dst, err);
+}
 
 static int undist_points_args(slam_ctx* c, const float* src, size_t src_stride, int n, const float* dst)
 {
@@ -1348,14 +1415,14 @@ static int undist_points_args(slam_ctx* c, const float* src, size_t src_stride, 
     return SLAM_OK;
 }
 
-int slam_undistort_points_dev(slam_ctx* c, void* stream, const float* d_src, size_t src_stride, int n, const double* K,
-                              const double* dist, int ndist, const double* P, int max_iter, double eps, float* d_dst,
-                              float* d_err)
+static int undistort_points_dev(slam_ctx* c, void* stream, const float* d_src, size_t src_stride, int n, const double* K,
+                                const double* dist, int ndist, const double* P, int max_iter, double eps, float* d_dst,
+                                float* d_err, int model)
 {
     if (!c) return SLAM_E_INVALID_ARG;
     if (int rc = undist_points_args(c, d_src, src_stride, n, d_dst)) return rc;
-    UndistPointsParams prm;
-    if (int rc = undist_points_params(c, K, dist, ndist, P, max_iter, eps, &prm)) return rc;
+    LensPointsParams prm;
+    if (int rc = lens_points_params(c, K, dist, ndist, P, max_iter, eps, model, &prm)) return rc;
     if (n == 0) return SLAM_OK;   // nothing to do: no launch
     const uintptr_t a = reinterpret_cast<uintptr_t>(d_src), b = reinterpret_cast<uintptr_t>(d_dst),
                     e = reinterpret_cast<uintptr_t>(d_err);
@@ -1368,18 +1435,18 @@ int slam_undistort_points_dev(slam_ctx* c, void* stream, const float* d_src, siz
         return set_err(c, SLAM_E_INVALID_ARG, "undistort points: points, results and residuals overlap");
     SLAM_HIP(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    SLAM_HIP(c, launch_undist_points(s, prm, d_src, src_stride, n, d_dst, d_err));
+    SLAM_HIP(c, launch_lens_points(s, prm, d_src, src_stride, n, d_dst, d_err));
     return SLAM_OK;
 }
 
-int slam_undistort_points(slam_ctx* c, const float* src, size_t src_stride, int n, const double* K, const double* dist,
-                          int ndist, const double* P, int max_iter, double eps, float* dst, float* err)
+static int undistort_points(slam_ctx* c, const float* src, size_t src_stride, int n, const double* K, const double* dist,
+                            int ndist, const double* P, int max_iter, double eps, float* dst, float* err, int model)
 {
     if (!c) return SLAM_E_INVALID_ARG;
     if (int rc = async_guard(c)) return rc;
     if (int rc = undist_points_args(c, src, src_stride, n, dst)) return rc;
-    UndistPointsParams prm;
-    if (int rc = undist_points_params(c, K, dist, ndist, P, max_iter, eps, &prm)) return rc;
+    LensPointsParams prm;
+    if (int rc = lens_points_params(c, K, dist, ndist, P, max_iter, eps, model, &prm)) return rc;
     if (n == 0) return SLAM_OK;
     SLAM_HIP(c, hipSetDevice(c->device));
     // device layout: the points at the caller's stride, then n x 2 results, then n residuals
@@ -1390,11 +1457,39 @@ int slam_undistort_points(slam_ctx* c, const float* src, size_t src_stride, int 
     float* d_dst = reinterpret_cast<float*>(base + sa);
     float* d_err = reinterpret_cast<float*>(base + sa + sb);
     SLAM_HIP(c, hipMemcpyAsync(d_src, src, (size_t)(n - 1) * src_stride + 8, hipMemcpyHostToDevice, c->stream));
-    SLAM_HIP(c, launch_undist_points(c->stream, prm, d_src, src_stride, n, d_dst, err ? d_err : nullptr));
+    SLAM_HIP(c, launch_lens_points(c->stream, prm, d_src, src_stride, n, d_dst, err ? d_err : nullptr));
     // dst may be src (stride 8): the upload above is complete before this copy lands
     SLAM_HIP(c, hipMemcpyAsync(dst, d_dst, sb, hipMemcpyDeviceToHost, c->stream));
     if (err) SLAM_HIP(c, hipMemcpyAsync(err, d_err, se, hipMemcpyDeviceToHost, c->stream));
     return stream_sync(c, c->stream);
+}
+
+int slam_undistort_points_dev(slam_ctx* c, void* stream, const float* d_src, size_t src_stride, int n, const double* K,
+                              const double* dist, int ndist, const double* P, int max_iter, double eps, float* d_dst,
+                              float* d_err)
+{
+    return undistort_points_dev(c, stream, d_src, src_stride, n, K, dist, ndist, P, max_iter, eps, d_dst, d_err, kLensBrown);
+}
+
+int slam_undistort_points(slam_ctx* c, const float* src, size_t src_stride, int n, const double* K, const double* dist,
+                          int ndist, const double* P, int max_iter, double eps, float* dst, float* err)
+{
+    return undistort_points(c, src, src_stride, n, K, dist, ndist, P, max_iter, eps, dst, err, kLensBrown);
+}
+
+int slam_fisheye_undistort_points_dev(slam_ctx* c, void* stream, const float* d_src, size_t src_stride, int n,
+                                      const double* K, const double* dist, int ndist, const double* P, int max_iter,
+                                      double eps, float* d_dst, float* d_err)
+{
+    return undistort_points_dev(c, stream, d_src, src_stride, n, K, dist, ndist, P, max_iter, eps, d_dst, d_err,
+                                kLensFisheye);
+}
+
+int slam_fisheye_undistort_points(slam_ctx* c, const float* src, size_t src_stride, int n, const double* K,
+                                  const double* dist, int ndist, const double* P, int max_iter, double eps, float* dst,
+                                  float* err)
+{
+    return undistort_points(c, src, src_stride, n, K, dist, ndist, P, max_iter, eps, dst, err, kLensFisheye);
 }
 
 // ---- chessboard calibration (calib.hip, calib_board.cpp, calib_solve.cpp) ----
@@ -1465,6 +1560,22 @@ int slam_label_chessboard(const int32_t* cand, int n, int scale, int board_w, in
         (long long)board_w * board_h > 4096)
         return SLAM_E_INVALID_ARG;
     *found = label_chessboard(cand, n, scale, board_w, board_h, corners) ? 1 : 0;
+    return SLAM_OK;
+}
+
+int slam_label_chessboard_grow(const int32_t* cand, int n, int scale, int board_w, int board_h, float* corners,
+                               int* found)
+{
+    // the growing labeller is cubic in the number of corners: boards of up to 256
+    if (!found || !corners || n < 0 || (n > 0 && !cand) || scale < 1 || board_w < 2 || board_h < 2 ||
+        (long long)board_w * board_h > 256)
+        return SLAM_E_INVALID_ARG;
+    // level coordinates (a level is at most 1024 pixels a side).  Within +-8192 a difference is below 2^14, a
+    // squared length below 2^29 and the largest product the labeller forms, 4 (u.w)^2, below 2^60
+    for (int i = 0; i < n; i++)
+        if (cand[3 * i] < -8192 || cand[3 * i] > 8192 || cand[3 * i + 1] < -8192 || cand[3 * i + 1] > 8192)
+            return SLAM_E_INVALID_ARG;
+    *found = label_chessboard_grow(cand, n, scale, board_w, board_h, corners) ? 1 : 0;
     return SLAM_OK;
 }
 
@@ -1599,6 +1710,12 @@ int slam_calibrate_camera(const float* obj, const float* img, int nviews, int np
                           double* D, double* rvecs, double* tvecs, double* rms, int* iterations)
 {
     return calibrate_camera(obj, img, nviews, npts, size_w, size_h, K, D, rvecs, tvecs, rms, iterations);
+}
+
+int slam_fisheye_calibrate(const float* obj, const float* img, int nviews, int npts, int size_w, int size_h, double* K,
+                           double* D, double* rvecs, double* tvecs, double* rms, int* iterations)
+{
+    return fisheye_calibrate(obj, img, nviews, npts, size_w, size_h, K, D, rvecs, tvecs, rms, iterations);
 }
 
 void* slam_context_stream(slam_ctx* c) { return c ? (void*)c->stream : nullptr; }

@@ -13,7 +13,15 @@
 // Jacobian of a view's rotation is d(R X)/d d = -[R X]x at d = 0: no derivative
 // of Rodrigues' formula is needed.  exp(d) and the final rotation vectors come
 // from slam_rodrigues (pnp.hip); there is no second Rodrigues here.
+//
+// fisheye_calibrate is the same optimisation for the
+// model of cv::fisheye::calibrate with the skew fixed at 0: fx fy cx cy, k1 k2
+// k3 k4 and the poses, through the same Levenberg-Marquardt loop.  Its initial
+// values are OpenCV's: f = max(w, h) / pi, the principal point at the centre,
+// poses from the homographies of the points undistorted with D = 0.
 #include "slamhip_internal.h"
+
+#include "fisheye_math.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -24,7 +32,8 @@ namespace slamhip {
 
 namespace {
 
-constexpr int kIntr = 9;   // fx fy cx cy k1 k2 p1 p2 k3
+constexpr int kIntr = 9;          // fx fy cx cy k1 k2 p1 p2 k3
+constexpr int kIntrFisheye = 8;   // fx fy cx cy k1 k2 k3 k4
 
 // in-place Gaussian elimination with partial pivoting of the n x n system A x = b; false: singular
 bool solve_dense(std::vector<double>& A, std::vector<double>& b, int n)
@@ -119,13 +128,60 @@ struct Problem {
     int nviews, npts;
     const float* obj;      // npts x 3, z = 0
     const float* img;      // nviews x npts x 2
+    int nintr;             // kIntr, or kIntrFisheye for the fisheye model
 };
 
-// residuals of one view and, when J != null, its Jacobian blocks: Ji 2 x 9 (intrinsics) and
+// view_terms for the fisheye model: u = fx a g(r) + cx, v = fy b g(r) + cy with (a, b) = (Yx, Yy) / Yz,
+// r = |(a, b)|, theta = atan r, g = theta_d / r (1 at r = 0); Ji is 2 x 8 per point
+void fisheye_terms(const Problem& P, int v, const double* in, const double* R, const double* t, double* res, double* Ji,
+                   double* Je)
+{
+    const double fx = in[0], fy = in[1], cx = in[2], cy = in[3];
+    const double* k = in + 4;
+    for (int i = 0; i < P.npts; i++) {
+        const double X = P.obj[3 * i], Y = P.obj[3 * i + 1];
+        const double Px = R[0] * X + R[1] * Y, Py = R[3] * X + R[4] * Y, Pz = R[6] * X + R[7] * Y;   // R X
+        const double Yx = Px + t[0], Yy = Py + t[1], Yz = Pz + t[2];
+        const double iz = 1.0 / Yz, a = Yx * iz, b = Yy * iz;
+        const double r = std::sqrt(a * a + b * b);
+        const double th = fe_atan(r);
+        const double t2 = th * th, t4 = t2 * t2, t6 = t4 * t2, t8 = t4 * t4;
+        const double td = th * (1.0 + k[0] * t2 + k[1] * t4 + k[2] * t6 + k[3] * t8);
+        const double g = r == 0 ? 1.0 : td / r;
+        const float* m = P.img + 2 * ((size_t)v * P.npts + i);
+        res[2 * i] = fx * a * g + cx - (double)m[0];
+        res[2 * i + 1] = fy * b * g + cy - (double)m[1];
+        if (!Ji) continue;
+        const double ir = r > 1e-12 ? 1.0 / r : 0.0;   // at the axis every derivative through r vanishes
+        const double p3 = th * t2 * ir, p5 = th * t4 * ir, p7 = th * t6 * ir, p9 = th * t8 * ir;
+        double* ji = Ji + 16 * (size_t)i;
+        const double row[16] = {a * g, 0, 1, 0, fx * a * p3, fx * a * p5, fx * a * p7, fx * a * p9,
+                                0, b * g, 0, 1, fy * b * p3, fy * b * p5, fy * b * p7, fy * b * p9};
+        std::memcpy(ji, row, sizeof(row));
+        const double q = 1.0 + 3 * k[0] * t2 + 5 * k[1] * t4 + 7 * k[2] * t6 + 9 * k[3] * t8;   // d theta_d / d theta
+        const double gp = (q / (1.0 + r * r) - g) * ir;                                        // d g / d r
+        const double mm = gp * ir;
+        const double xx = g + a * a * mm, xy = a * b * mm, yy = g + b * b * mm;
+        const double ux = fx * xx * iz, uy = fx * xy * iz, uz = -fx * (xx * a + xy * b) * iz;
+        const double vx = fy * xy * iz, vy = fy * yy * iz, vz = -fy * (xy * a + yy * b) * iz;
+        double* je = Je + 12 * (size_t)i;
+        je[0] = -uy * Pz + uz * Py;
+        je[1] = ux * Pz - uz * Px;
+        je[2] = -ux * Py + uy * Px;
+        je[3] = ux; je[4] = uy; je[5] = uz;
+        je[6] = -vy * Pz + vz * Py;
+        je[7] = vx * Pz - vz * Px;
+        je[8] = -vx * Py + vy * Px;
+        je[9] = vx; je[10] = vy; je[11] = vz;
+    }
+}
+
+// residuals of one view and, when J != null, its Jacobian blocks: Ji 2 x nintr (intrinsics) and
 // Je 2 x 6 (rotation step d, translation) per point
 void view_terms(const Problem& P, int v, const double* in, const double* R, const double* t, double* res, double* Ji,
                 double* Je)
 {
+    if (P.nintr == kIntrFisheye) return fisheye_terms(P, v, in, R, t, res, Ji, Je);
     const double fx = in[0], fy = in[1], cx = in[2], cy = in[3];
     const double k1 = in[4], k2 = in[5], p1 = in[6], p2 = in[7], k3 = in[8];
     for (int i = 0; i < P.npts; i++) {
@@ -176,6 +232,117 @@ double total_cost(const Problem& P, const double* in, const std::vector<double>&
     return c;
 }
 
+// the pose of each view from its homography H (board plane -> pixels, or -> normalised
+// coordinates with fx = fy = 1, cx = cy = 0): K^-1 H orthonormalised; a SLAM_* code
+int poses_from_homographies(const std::vector<double>& Hs, int nviews, double fx, double fy, double cx0, double cy0,
+                            std::vector<double>& R, std::vector<double>& t)
+{
+    const double in[2] = {fx, fy};
+    for (int v = 0; v < nviews; v++) {
+        const double* H = &Hs[9 * (size_t)v];
+        double M[9];   // K^-1 H
+        for (int k = 0; k < 3; k++) {
+            M[k] = (H[k] - cx0 * H[6 + k]) / in[0];
+            M[3 + k] = (H[3 + k] - cy0 * H[6 + k]) / in[1];
+            M[6 + k] = H[6 + k];
+        }
+        const double sgn = M[8] < 0 ? -1.0 : 1.0;   // the board is in front of the camera
+        double r1[3] = {M[0], M[3], M[6]}, r2[3] = {M[1], M[4], M[7]};
+        const double lam = sgn / std::sqrt(r1[0] * r1[0] + r1[1] * r1[1] + r1[2] * r1[2]);
+        if (!std::isfinite(lam)) return SLAM_E_SOLVER;
+        for (int k = 0; k < 3; k++) { r1[k] *= lam; r2[k] *= lam; t[3 * (size_t)v + k] = M[3 * k + 2] * lam; }
+        // Gram-Schmidt: r1, then r2 made orthogonal to it, r3 = r1 x r2
+        const double n1 = std::sqrt(r1[0] * r1[0] + r1[1] * r1[1] + r1[2] * r1[2]);
+        for (int k = 0; k < 3; k++) r1[k] /= n1;
+        const double dt = r1[0] * r2[0] + r1[1] * r2[1] + r1[2] * r2[2];
+        for (int k = 0; k < 3; k++) r2[k] -= dt * r1[k];
+        const double n2 = std::sqrt(r2[0] * r2[0] + r2[1] * r2[1] + r2[2] * r2[2]);
+        if (!(n2 > 1e-12) || !std::isfinite(n2)) return SLAM_E_SOLVER;
+        for (int k = 0; k < 3; k++) r2[k] /= n2;
+        const double r3[3] = {r1[1] * r2[2] - r1[2] * r2[1], r1[2] * r2[0] - r1[0] * r2[2], r1[0] * r2[1] - r1[1] * r2[0]};
+        double* Rv = &R[9 * (size_t)v];
+        for (int k = 0; k < 3; k++) { Rv[3 * k] = r1[k]; Rv[3 * k + 1] = r2[k]; Rv[3 * k + 2] = r3[k]; }
+    }
+
+    return SLAM_OK;
+}
+
+// Levenberg-Marquardt from (in, R, t) to the optimum; a SLAM_* code
+int refine(const Problem& P, double* in, std::vector<double>& R, std::vector<double>& t, double* cost_out, int* it_out)
+{
+    const int nviews = P.nviews, npts = P.npts, ni = P.nintr;
+    const int np = ni + 6 * nviews;
+    std::vector<double> res(2 * (size_t)npts), Ji(2 * (size_t)ni * npts), Je(12 * (size_t)npts);
+    std::vector<double> JtJ((size_t)np * np), g(np), A, step(np), Rn(R.size()), tn(t.size());
+    double cost = total_cost(P, in, R, t, res);
+    if (!std::isfinite(cost)) return SLAM_E_SOLVER;
+    double lambda = 1e-3;
+    int it = 0, stalled = 0;
+    const int kMaxIter = 500;
+    for (; it < kMaxIter && stalled < 3; it++) {
+        std::fill(JtJ.begin(), JtJ.end(), 0.0);
+        std::fill(g.begin(), g.end(), 0.0);
+        for (int v = 0; v < nviews; v++) {
+            view_terms(P, v, in, &R[9 * (size_t)v], &t[3 * (size_t)v], res.data(), Ji.data(), Je.data());
+            const int e0 = ni + 6 * v;
+            for (int r = 0; r < 2 * npts; r++) {
+                const double* ji = &Ji[(size_t)ni * r];
+                const double* je = &Je[6 * (size_t)r];
+                for (int a = 0; a < ni; a++) {
+                    for (int b = a; b < ni; b++) JtJ[(size_t)a * np + b] += ji[a] * ji[b];
+                    for (int b = 0; b < 6; b++) JtJ[(size_t)a * np + e0 + b] += ji[a] * je[b];
+                    g[a] += ji[a] * res[r];
+                }
+                for (int a = 0; a < 6; a++) {
+                    for (int b = a; b < 6; b++) JtJ[(size_t)(e0 + a) * np + e0 + b] += je[a] * je[b];
+                    g[e0 + a] += je[a] * res[r];
+                }
+            }
+        }
+        for (int a = 0; a < np; a++)
+            for (int b = 0; b < a; b++) JtJ[(size_t)a * np + b] = JtJ[(size_t)b * np + a];
+        bool accepted = false;
+        for (int tries = 0; tries < 40 && !accepted; tries++) {
+            A = JtJ;
+            for (int a = 0; a < np; a++) {
+                const double d = JtJ[(size_t)a * np + a];
+                A[(size_t)a * np + a] = d + lambda * (d > 0 ? d : 1.0);
+                step[a] = -g[a];
+            }
+            if (solve_dense(A, step, np)) {
+                double inn[kIntr];
+                for (int a = 0; a < ni; a++) inn[a] = in[a] + step[a];
+                bool fine = true;
+                for (int v = 0; v < nviews && fine; v++) {
+                    const double* d = &step[ni + 6 * (size_t)v];
+                    double E[9];
+                    if (slam_rodrigues(d, 3, E) != SLAM_OK) { fine = false; break; }
+                    mul33(E, &R[9 * (size_t)v], &Rn[9 * (size_t)v]);
+                    for (int k = 0; k < 3; k++) tn[3 * (size_t)v + k] = t[3 * (size_t)v + k] + d[3 + k];
+                }
+                const double cn = fine ? total_cost(P, inn, Rn, tn, res) : INFINITY;
+                if (std::isfinite(cn) && cn <= cost) {
+                    // converged when accepted steps stop lowering the cost
+                    stalled = (cost - cn <= 1e-15 * cost) ? stalled + 1 : 0;
+                    std::memcpy(in, inn, ni * sizeof(double));
+                    R.swap(Rn);
+                    t.swap(tn);
+                    cost = cn;
+                    lambda = std::max(lambda * 0.1, 1e-12);
+                    accepted = true;
+                    break;
+                }
+            }
+            lambda *= 10;
+        }
+        if (!accepted) break;   // no downhill step at any damping: a minimum to rounding
+    }
+
+    *cost_out = cost;
+    *it_out = it;
+    return SLAM_OK;
+}
+
 }  // namespace
 
 int calibrate_camera(const float* obj, const float* img, int nviews, int npts, int size_w, int size_h, double* K,
@@ -188,7 +355,7 @@ int calibrate_camera(const float* obj, const float* img, int nviews, int npts, i
             return SLAM_E_INVALID_ARG;            // a planar target with z = 0
     for (size_t i = 0; i < (size_t)nviews * npts * 2; i++)
         if (!std::isfinite(img[i])) return SLAM_E_INVALID_ARG;
-    const Problem P{nviews, npts, obj, img};
+    const Problem P{nviews, npts, obj, img, kIntr};
 
     // ---- initial values ----
     std::vector<double> xy(2 * (size_t)npts), uv(2 * (size_t)npts), Hs(9 * (size_t)nviews);
@@ -226,99 +393,11 @@ int calibrate_camera(const float* obj, const float* img, int nviews, int npts, i
     if (!std::isfinite(in[0]) || !std::isfinite(in[1])) return SLAM_E_SOLVER;
 
     std::vector<double> R(9 * (size_t)nviews), t(3 * (size_t)nviews);
-    for (int v = 0; v < nviews; v++) {
-        const double* H = &Hs[9 * (size_t)v];
-        double M[9];   // K^-1 H
-        for (int k = 0; k < 3; k++) {
-            M[k] = (H[k] - cx0 * H[6 + k]) / in[0];
-            M[3 + k] = (H[3 + k] - cy0 * H[6 + k]) / in[1];
-            M[6 + k] = H[6 + k];
-        }
-        const double sgn = M[8] < 0 ? -1.0 : 1.0;   // the board is in front of the camera
-        double r1[3] = {M[0], M[3], M[6]}, r2[3] = {M[1], M[4], M[7]};
-        const double lam = sgn / std::sqrt(r1[0] * r1[0] + r1[1] * r1[1] + r1[2] * r1[2]);
-        if (!std::isfinite(lam)) return SLAM_E_SOLVER;
-        for (int k = 0; k < 3; k++) { r1[k] *= lam; r2[k] *= lam; t[3 * (size_t)v + k] = M[3 * k + 2] * lam; }
-        // Gram-Schmidt: r1, then r2 made orthogonal to it, r3 = r1 x r2
-        const double n1 = std::sqrt(r1[0] * r1[0] + r1[1] * r1[1] + r1[2] * r1[2]);
-        for (int k = 0; k < 3; k++) r1[k] /= n1;
-        const double dt = r1[0] * r2[0] + r1[1] * r2[1] + r1[2] * r2[2];
-        for (int k = 0; k < 3; k++) r2[k] -= dt * r1[k];
-        const double n2 = std::sqrt(r2[0] * r2[0] + r2[1] * r2[1] + r2[2] * r2[2]);
-        if (!(n2 > 1e-12) || !std::isfinite(n2)) return SLAM_E_SOLVER;
-        for (int k = 0; k < 3; k++) r2[k] /= n2;
-        const double r3[3] = {r1[1] * r2[2] - r1[2] * r2[1], r1[2] * r2[0] - r1[0] * r2[2], r1[0] * r2[1] - r1[1] * r2[0]};
-        double* Rv = &R[9 * (size_t)v];
-        for (int k = 0; k < 3; k++) { Rv[3 * k] = r1[k]; Rv[3 * k + 1] = r2[k]; Rv[3 * k + 2] = r3[k]; }
-    }
+    if (int rc = poses_from_homographies(Hs, nviews, in[0], in[1], cx0, cy0, R, t)) return rc;
 
-    // ---- Levenberg-Marquardt ----
-    const int np = kIntr + 6 * nviews;
-    std::vector<double> res(2 * (size_t)npts), Ji(18 * (size_t)npts), Je(12 * (size_t)npts);
-    std::vector<double> JtJ((size_t)np * np), g(np), A, step(np), Rn(R.size()), tn(t.size());
-    double cost = total_cost(P, in, R, t, res);
-    if (!std::isfinite(cost)) return SLAM_E_SOLVER;
-    double lambda = 1e-3;
-    int it = 0, stalled = 0;
-    const int kMaxIter = 500;
-    for (; it < kMaxIter && stalled < 3; it++) {
-        std::fill(JtJ.begin(), JtJ.end(), 0.0);
-        std::fill(g.begin(), g.end(), 0.0);
-        for (int v = 0; v < nviews; v++) {
-            view_terms(P, v, in, &R[9 * (size_t)v], &t[3 * (size_t)v], res.data(), Ji.data(), Je.data());
-            const int e0 = kIntr + 6 * v;
-            for (int r = 0; r < 2 * npts; r++) {
-                const double* ji = &Ji[9 * (size_t)r];
-                const double* je = &Je[6 * (size_t)r];
-                for (int a = 0; a < kIntr; a++) {
-                    for (int b = a; b < kIntr; b++) JtJ[(size_t)a * np + b] += ji[a] * ji[b];
-                    for (int b = 0; b < 6; b++) JtJ[(size_t)a * np + e0 + b] += ji[a] * je[b];
-                    g[a] += ji[a] * res[r];
-                }
-                for (int a = 0; a < 6; a++) {
-                    for (int b = a; b < 6; b++) JtJ[(size_t)(e0 + a) * np + e0 + b] += je[a] * je[b];
-                    g[e0 + a] += je[a] * res[r];
-                }
-            }
-        }
-        for (int a = 0; a < np; a++)
-            for (int b = 0; b < a; b++) JtJ[(size_t)a * np + b] = JtJ[(size_t)b * np + a];
-        bool accepted = false;
-        for (int tries = 0; tries < 40 && !accepted; tries++) {
-            A = JtJ;
-            for (int a = 0; a < np; a++) {
-                const double d = JtJ[(size_t)a * np + a];
-                A[(size_t)a * np + a] = d + lambda * (d > 0 ? d : 1.0);
-                step[a] = -g[a];
-            }
-            if (solve_dense(A, step, np)) {
-                double inn[kIntr];
-                for (int a = 0; a < kIntr; a++) inn[a] = in[a] + step[a];
-                bool fine = true;
-                for (int v = 0; v < nviews && fine; v++) {
-                    const double* d = &step[kIntr + 6 * (size_t)v];
-                    double E[9];
-                    if (slam_rodrigues(d, 3, E) != SLAM_OK) { fine = false; break; }
-                    mul33(E, &R[9 * (size_t)v], &Rn[9 * (size_t)v]);
-                    for (int k = 0; k < 3; k++) tn[3 * (size_t)v + k] = t[3 * (size_t)v + k] + d[3 + k];
-                }
-                const double cn = fine ? total_cost(P, inn, Rn, tn, res) : INFINITY;
-                if (std::isfinite(cn) && cn <= cost) {
-                    // converged when accepted steps stop lowering the cost
-                    stalled = (cost - cn <= 1e-15 * cost) ? stalled + 1 : 0;
-                    std::memcpy(in, inn, sizeof(in));
-                    R.swap(Rn);
-                    t.swap(tn);
-                    cost = cn;
-                    lambda = std::max(lambda * 0.1, 1e-12);
-                    accepted = true;
-                    break;
-                }
-            }
-            lambda *= 10;
-        }
-        if (!accepted) break;   // no downhill step at any damping: a minimum to rounding
-    }
+    double cost = 0;
+    int it = 0;
+    if (int rc = refine(P, in, R, t, &cost, &it)) return rc;
 
     const double k[9] = {in[0], 0, in[2], 0, in[1], in[3], 0, 0, 1};
     std::memcpy(K, k, sizeof(k));
@@ -328,6 +407,56 @@ int calibrate_camera(const float* obj, const float* img, int nviews, int npts, i
         std::memcpy(tvecs + 3 * (size_t)v, &t[3 * (size_t)v], 3 * sizeof(double));
     }
     for (int a = 0; a < kIntr; a++)
+        if (!std::isfinite(in[a])) return SLAM_E_SOLVER;
+    *rms = std::sqrt(cost / ((double)nviews * npts));
+    *iterations = it;
+    return SLAM_OK;
+}
+
+int fisheye_calibrate(const float* obj, const float* img, int nviews, int npts, int size_w, int size_h, double* K,
+                      double* D, double* rvecs, double* tvecs, double* rms, int* iterations)
+{
+    if (!obj || !img || !K || !D || !rvecs || !tvecs || !rms || !iterations) return SLAM_E_INVALID_ARG;
+    if (nviews < 3 || npts < 4 || size_w <= 0 || size_h <= 0) return SLAM_E_INVALID_ARG;
+    for (int i = 0; i < npts; i++)
+        if (obj[3 * i + 2] != 0.f || !std::isfinite(obj[3 * i]) || !std::isfinite(obj[3 * i + 1]))
+            return SLAM_E_INVALID_ARG;            // a planar target with z = 0
+    for (size_t i = 0; i < (size_t)nviews * npts * 2; i++)
+        if (!std::isfinite(img[i])) return SLAM_E_INVALID_ARG;
+    const Problem P{nviews, npts, obj, img, kIntrFisheye};
+
+    // ---- initial values: f = max(w, h) / pi, the centre, D = 0; poses from the homographies
+    // board -> normalised coordinates of the points undistorted with D = 0 (theta = |pw|, below 1.5) ----
+    const double f0 = std::max(size_w, size_h) / 3.14159265358979323846;
+    double in[kIntr] = {f0, f0, (size_w - 1) * 0.5, (size_h - 1) * 0.5, 0, 0, 0, 0, 0};
+    std::vector<double> xy(2 * (size_t)npts), uv(2 * (size_t)npts), Hs(9 * (size_t)nviews);
+    for (int i = 0; i < npts; i++) { xy[2 * i] = obj[3 * i]; xy[2 * i + 1] = obj[3 * i + 1]; }
+    for (int v = 0; v < nviews; v++) {
+        for (int i = 0; i < npts; i++) {
+            const float* m = img + 2 * ((size_t)v * npts + i);
+            const double px = ((double)m[0] - in[2]) / f0, py = ((double)m[1] - in[3]) / f0;
+            const double th = std::sqrt(px * px + py * py);
+            const double sc = th > 1e-9 ? fe_tan(std::min(th, 1.5)) / th : 1.0;
+            uv[2 * i] = px * sc;
+            uv[2 * i + 1] = py * sc;
+        }
+        if (!homography(xy.data(), uv.data(), npts, &Hs[9 * (size_t)v])) return SLAM_E_SOLVER;
+    }
+    std::vector<double> R(9 * (size_t)nviews), t(3 * (size_t)nviews);
+    if (int rc = poses_from_homographies(Hs, nviews, 1.0, 1.0, 0.0, 0.0, R, t)) return rc;
+
+    double cost = 0;
+    int it = 0;
+    if (int rc = refine(P, in, R, t, &cost, &it)) return rc;
+
+    const double k[9] = {in[0], 0, in[2], 0, in[1], in[3], 0, 0, 1};
+    std::memcpy(K, k, sizeof(k));
+    std::memcpy(D, in + 4, 4 * sizeof(double));
+    for (int v = 0; v < nviews; v++) {
+        if (slam_rodrigues(&R[9 * (size_t)v], 9, rvecs + 3 * (size_t)v) != SLAM_OK) return SLAM_E_SOLVER;
+        std::memcpy(tvecs + 3 * (size_t)v, &t[3 * (size_t)v], 3 * sizeof(double));
+    }
+    for (int a = 0; a < kIntrFisheye; a++)
         if (!std::isfinite(in[a])) return SLAM_E_SOLVER;
     *rms = std::sqrt(cost / ((double)nviews * npts));
     *iterations = it;

@@ -294,7 +294,8 @@ struct slam_ctx {
     slamhip::DevBuf undist_out;           // slam_undistort: the device result of a host frame
     slamhip::DevBuf undist_pts;           // slam_undistort_points: the host points and their results
     bool undist_valid = false;
-    double undist_key[30] = {};           // K, newK (K when absent), the 12 coefficients
+    double undist_key[30] = {};           // K, newK (K when absent), the 12 coefficients (fisheye: 4, then zeros)
+    int undist_model = 0;                 // kLensBrown or kLensFisheye: part of the key
     int undist_w = 0, undist_h = 0;
     bool undist_used = false;             // undist_ev has been recorded
     hipStream_t undist_stream = nullptr;  // the stream that last built or read the map
@@ -512,6 +513,41 @@ int pnp_ransac(slam_ctx* c, const float* op, const float* ip, int n, const doubl
                int* found);
 
 // ---- undistortion (undistort.hip) ----
+// the lens model of the context's cached map
+constexpr int kLensBrown = 0, kLensFisheye = 1;
+
+// cv::invert's closed form for 3x3 (DECOMP_LU takes it too); false: det == 0
+__host__ __device__ inline bool invert3(const double* a, double* ir)
+{
+    double d = a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) +
+               a[2] * (a[3] * a[7] - a[4] * a[6]);
+    if (d == 0) return false;
+    d = 1. / d;
+    ir[0] = (a[4] * a[8] - a[5] * a[7]) * d;
+    ir[1] = (a[2] * a[7] - a[1] * a[8]) * d;
+    ir[2] = (a[1] * a[5] - a[2] * a[4]) * d;
+    ir[3] = (a[5] * a[6] - a[3] * a[8]) * d;
+    ir[4] = (a[0] * a[8] - a[2] * a[6]) * d;
+    ir[5] = (a[2] * a[3] - a[0] * a[5]) * d;
+    ir[6] = (a[3] * a[7] - a[4] * a[6]) * d;
+    ir[7] = (a[1] * a[6] - a[0] * a[7]) * d;
+    ir[8] = (a[0] * a[4] - a[1] * a[3]) * d;
+    return true;
+}
+
+// cvRound as the x86 conversion gives it: nearest even; a value outside int, or
+// a NaN, is INT_MIN (__double2int_rn would clamp)
+__device__ __forceinline__ int cv_round(double v)
+{
+    const double r = rint(v);
+    return (r >= -2147483648.0 && r <= 2147483647.0) ? (int)r : (-2147483647 - 1);
+}
+
+// makes the context's cached map that of (model, key, w, h): on a miss `build`
+// launches the map kernel on s into undist_xy / undist_frac (already sized);
+// orders s after the map's last use on another stream.  Returns a SLAM_* code
+int undist_cached_map(slam_ctx* c, hipStream_t s, int w, int h, const double (&key)[30], int model,
+                      const std::function<hipError_t()>& build);
 // validates the camera model and makes the context's cached map that of
 // (K, newK, D, w, h), building it on s when anything changed; returns a SLAM_* code
 int undist_prepare(slam_ctx* c, hipStream_t s, int w, int h, const double* K, const double* dist, int ndist,
@@ -537,6 +573,23 @@ int undist_points_params(slam_ctx* c, const double* K, const double* dist, int n
 hipError_t launch_undist_points(hipStream_t s, const UndistPointsParams& P, const float* src, size_t src_stride, int n,
                                 float* dst, float* err);
 
+// ---- the fisheye lens model (fisheye.hip) ----
+// undist_prepare for cv::fisheye (ndist == 4, finite; newK's last row (0, 0, 1)): the map goes to the same cache
+int fisheye_prepare(slam_ctx* c, hipStream_t s, int w, int h, const double* K, const double* dist, int ndist,
+                    const double* newK);
+struct FisheyePointsParams {
+    double fx, fy, cx, cy;
+    double k[4];
+    double RR[9];
+    double eps;
+    int max_iter, use_eps;
+};
+int fisheye_points_params(slam_ctx* c, const double* K, const double* dist, int ndist, const double* P, int max_iter,
+                          double eps, FisheyePointsParams* out);
+// as launch_undist_points; a rejected point is (-1000000, -1000000) with a NaN residual
+hipError_t launch_fisheye_points(hipStream_t s, const FisheyePointsParams& P, const float* src, size_t src_stride, int n,
+                                 float* dst, float* err);
+
 // ---- chessboard calibration (calib.hip, calib_board.cpp, calib_solve.cpp) ----
 // the level's downscale s = max(1, ceil(max(w, h) / 1024)) and the candidate bound
 // ceil(W / 8) * ceil(H / 8) of a W x H level (two candidates are never within
@@ -554,9 +607,15 @@ hipError_t launch_calib_subpix(hipStream_t s, const uint8_t* img, size_t row_str
 // the board_w * board_h strongest of n candidates labelled as a lattice (calib_board.cpp):
 // corners in full-resolution pixels, canonical order; false: no complete board
 bool label_chessboard(const int32_t* cand, int n, int scale, int board_w, int board_h, float* corners);
+// the same from the 2 * board_w * board_h strongest by growing a lattice from a seed, for
+// boards a lens bends (tests/fisheye_ref.py label_board_grow is the definition)
+bool label_chessboard_grow(const int32_t* cand, int n, int scale, int board_w, int board_h, float* corners);
 // calibrateCamera's optimum (calib_solve.cpp); returns a SLAM_* code
 int calibrate_camera(const float* obj, const float* img, int nviews, int npts, int size_w, int size_h, double* K,
                      double* D, double* rvecs, double* tvecs, double* rms, int* iterations);
+// the same for the model of cv::fisheye::calibrate with the skew fixed at 0: K, D 4 (k1 k2 k3 k4)
+int fisheye_calibrate(const float* obj, const float* img, int nviews, int npts, int size_w, int size_h, double* K,
+                      double* D, double* rvecs, double* tvecs, double* rms, int* iterations);
 
 // ---- pyramidal Lucas-Kanade tracking (klt.hip) ----
 // one frame's pyramid: level l is w[l] x h[l] unpadded 8-bit pixels at pixel offset off[l];

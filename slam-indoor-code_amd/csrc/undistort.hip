@@ -38,33 +38,6 @@ struct UndistParams {
     int w, h, stripe;
 };
 
-// cv::invert's closed form for 3x3 (DECOMP_LU takes it too); false: det == 0
-__host__ __device__ inline bool invert3(const double* a, double* ir)
-{
-    double d = a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) +
-               a[2] * (a[3] * a[7] - a[4] * a[6]);
-    if (d == 0) return false;
-    d = 1. / d;
-    ir[0] = (a[4] * a[8] - a[5] * a[7]) * d;
-    ir[1] = (a[2] * a[7] - a[1] * a[8]) * d;
-    ir[2] = (a[1] * a[5] - a[2] * a[4]) * d;
-    ir[3] = (a[5] * a[6] - a[3] * a[8]) * d;
-    ir[4] = (a[0] * a[8] - a[2] * a[6]) * d;
-    ir[5] = (a[2] * a[3] - a[0] * a[5]) * d;
-    ir[6] = (a[3] * a[7] - a[4] * a[6]) * d;
-    ir[7] = (a[1] * a[6] - a[0] * a[7]) * d;
-    ir[8] = (a[0] * a[4] - a[1] * a[3]) * d;
-    return true;
-}
-
-// cvRound as the x86 conversion gives it: nearest even; a value outside int, or
-// a NaN, is INT_MIN (__double2int_rn would clamp)
-__device__ __forceinline__ int cv_round(double v)
-{
-    const double r = rint(v);
-    return (r >= -2147483648.0 && r <= 2147483647.0) ? (int)r : INT_MIN;
-}
-
 constexpr int kMapThreads = 64;
 
 __global__ __launch_bounds__(kMapThreads) void undist_map(UndistParams P, uint32_t* __restrict__ xy,
@@ -325,8 +298,16 @@ int undist_prepare(slam_ctx* c, hipStream_t s, int w, int h, const double* K, co
         if (!invert3(a, ir)) return set_err(c, SLAM_E_INVALID_ARG, "undistort: singular new camera matrix");
     }
     static_assert(sizeof(P.A) + sizeof(P.Ar) + sizeof(P.D) == sizeof(c->undist_key), "cache key layout");
-    const bool hit = c->undist_valid && c->undist_w == w && c->undist_h == h &&
-                     std::memcmp(c->undist_key, P.A, sizeof(c->undist_key)) == 0;
+    double key[30];
+    std::memcpy(key, P.A, sizeof(key));
+    return undist_cached_map(c, s, w, h, key, kLensBrown, [&] { return build_map(c, s, P); });
+}
+
+int undist_cached_map(slam_ctx* c, hipStream_t s, int w, int h, const double (&key)[30], int model,
+                      const std::function<hipError_t()>& build)
+{
+    const bool hit = c->undist_valid && c->undist_model == model && c->undist_w == w && c->undist_h == h &&
+                     std::memcmp(c->undist_key, key, sizeof(c->undist_key)) == 0;
     if (!c->undist_ev) SLAM_HIP(c, hipEventCreateWithFlags(&c->undist_ev, hipEventDisableTiming));
     if (!hit) {
         c->undist_valid = false;
@@ -334,8 +315,9 @@ int undist_prepare(slam_ctx* c, hipStream_t s, int w, int h, const double* K, co
         if (c->undist_used && c->undist_stream != s) SLAM_HIP(c, hipStreamWaitEvent(s, c->undist_ev, 0));
         SLAM_HIP(c, c->undist_xy.ensure((size_t)w * h * sizeof(uint32_t)));
         SLAM_HIP(c, c->undist_frac.ensure((size_t)w * h * sizeof(uint16_t)));
-        SLAM_HIP(c, build_map(c, s, P));
-        std::memcpy(c->undist_key, P.A, sizeof(c->undist_key));
+        SLAM_HIP(c, build());
+        std::memcpy(c->undist_key, key, sizeof(c->undist_key));
+        c->undist_model = model;
         c->undist_w = w;
         c->undist_h = h;
         c->undist_valid = true;

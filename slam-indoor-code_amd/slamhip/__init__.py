@@ -22,9 +22,11 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
                   clusterizePoints, clusterLabels, getBestFittingPlaneByPoints, planeMoments, projectToPlane,
                   delaunay2d, delaunay2dHost, delaunayStats, delaunayPredicates, meshFilter,
                   load_calibration, undistort, undistortBatch, undistortMap, undistortPoints,
+                  fisheyeUndistort, fisheyeUndistortBatch, fisheyeUndistortMap, fisheyeUndistortPoints,
+                  fisheyeCalibrate,
                   chessCandidates, labelChessboard, findChessboardCorners, cornerSubPix, calibrateCamera,
                   buildOpticalFlowPyramid, calcOpticalFlowPyrLK, kltLevelSizes,
-                  save_calibration,
+                  save_calibration, calibration_model,
                   imdecode, imread, imdecode_batch, jpegInfo, jpegLastTiming, applyOrientation,
                   renderViews, renderCamera, renderStats)
 from .config import ConfigError, ConfigService, reference_example

@@ -144,14 +144,21 @@ SIGNATURES = {
     "slam_undistort_map": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P]),
     "slam_undistort_points": (_I, [_P, _P, _SZ, _I, _P, _P, _I, _P, _I, _D, _P, _P]),
     "slam_undistort_points_dev": (_I, [_P, _P, _P, _SZ, _I, _P, _P, _I, _P, _I, _D, _P, _P]),
+    "slam_fisheye_undistort_batch": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "slam_fisheye_undistort": (_I, [_P, _P, _I, _I, _SZ, _I, _P, _P, _I, _P, _P, _SZ]),
+    "slam_fisheye_undistort_map": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "slam_fisheye_undistort_points": (_I, [_P, _P, _SZ, _I, _P, _P, _I, _P, _I, _D, _P, _P]),
+    "slam_fisheye_undistort_points_dev": (_I, [_P, _P, _P, _SZ, _I, _P, _P, _I, _P, _I, _D, _P, _P]),
     "slam_chess_candidates": (_I, [_P, _P, _I, _I, _SZ, _I, _P, _I, _P, _P]),
     "slam_chess_candidates_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P]),
     "slam_label_chessboard": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "slam_label_chessboard_grow": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "slam_find_chessboard": (_I, [_P, _P, _I, _I, _SZ, _I, _I, _I, _P, _P]),
     "slam_find_chessboard_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "slam_corner_subpix": (_I, [_P, _P, _I, _I, _SZ, _I, _P, _I, _I, _I, _I, _I, _I, _D]),
     "slam_corner_subpix_dev": (_I, [_P, _P, _P, _I, _I, _SZ, _I, _P, _I, _I, _I, _I, _I, _I, _D]),
     "slam_calibrate_camera": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "slam_fisheye_calibrate": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "slam_klt_pyramid": (_I, [_P, _P, _I, _I, _SZ, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "slam_klt_track": (_I, [_P, _P, _SZ, _P, _SZ, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _D, _I, _D]),
     "slam_klt_track_dev": (_I, [_P, _P, _P, _P, _I, _I, _SZ, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _D, _I, _D]),

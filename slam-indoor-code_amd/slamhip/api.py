@@ -698,15 +698,35 @@ def meshFilter(points, tris, max_size=MESH_MAX_SIZE):
 
 # ---- calibration file and undistortion (the batch.cpp:244 seam) ----------------
 
-def load_calibration(path, key="K"):
+def calibration_model(path):
+    """the lens model a calibration file names: the text of its string node
+    <model> ("fisheye": DC holds k1 k2 k3 k4 of cv::fisheye), or None for a file
+    without the node, which is the Brown-Conrady polynomial as the reference
+    writes it (DC: k1 k2 p1 p2 k3)"""
+    import xml.etree.ElementTree as ET
+    node = ET.parse(path).getroot().find("model")
+    if node is None:
+        return None
+    name = (node.text or "").strip().strip('"')
+    if name != "fisheye":
+        raise ValueError(f"{path}: unknown lens model {name!r}")
+    return name
+
+
+def load_calibration(path, key="K", model=None):
     """loadMatrixFromXML (IOmisc.cpp:80-88): the matrix `key` of an OpenCV XML
     storage as float64.  load_calibration(path) is the camera matrix K that
     defineCalibrationMatrix reads; "DC" the distortion coefficients that
     saveCalibParametersToXML writes beside it (IOmisc.cpp:68-76).  Reads
     opencv-matrix nodes of doubles: <dt> "d", or "<n>d" for n channels, which
     become n columns per element (R, 13x1 of "3d": 13 x 3).  A missing key raises
-    KeyError."""
+    KeyError.  model: the lens model the caller reads the coefficients for, None
+    (the polynomial) or "fisheye"; "DC" of a file that names another model
+    (calibration_model) raises ValueError, so that four fisheye coefficients are
+    never taken for k1 k2 p1 p2 or the reverse."""
     import xml.etree.ElementTree as ET
+    if key == "DC" and calibration_model(path) != model:
+        raise ValueError(f"{path}: the coefficients are of lens model {calibration_model(path)!r}, not {model!r}")
     node = ET.parse(path).getroot().find(key)
     if node is None:
         raise KeyError(f"{path}: no matrix {key!r}")
@@ -736,15 +756,25 @@ def _camera(K, dist, newK):
     return K, d, n
 
 
+def _entry(name, fisheye):
+    """the C entry `slam_<name>` of the Brown-Conrady model, or its fisheye twin"""
+    return getattr(lib(), ("slam_fisheye_" if fisheye else "slam_") + name)
+
+
 def undistortMap(w, h, K, dist, newK=None, ctx=None):
     """the fixed-point map of cv::undistort(src, dst, K, dist, newK) for w x h
     frames (slam_undistort_map): xy (h, w, 2) int16 source x, y and frac (h, w)
     uint16, (fy << 5) | fx.  Built on the device, cached in the context."""
+    return _undistortMap(False, w, h, K, dist, newK, ctx)
+
+
+def _undistortMap(fisheye, w, h, K, dist, newK, ctx):
+    """undistortMap, or its twin for the fisheye lens model"""
     c = _ctx(ctx)
     K, d, n = _camera(K, dist, newK)
     xy = np.empty((h, w, 2), np.int16)
     frac = np.empty((h, w), np.uint16)
-    check(lib().slam_undistort_map(c, int(w), int(h), ptr(K), ptr(d), d.size, ptr(n), ptr(xy), ptr(frac)), c)
+    check(_entry("undistort_map", fisheye)(c, int(w), int(h), ptr(K), ptr(d), d.size, ptr(n), ptr(xy), ptr(frac)), c)
     return xy, frac
 
 
@@ -752,6 +782,11 @@ def undistort(frame, K, dist, newK=None, ctx=None):
     """cv::undistort(frame, out, K, dist, newK) of an 8-bit gray or BGR frame in
     host memory (slam_undistort); the seam the reference marks at batch.cpp:244.
     Rows may be strided (a column range of a wider image)."""
+    return _undistort(False, frame, K, dist, newK, ctx)
+
+
+def _undistort(fisheye, frame, K, dist, newK, ctx):
+    """undistort, or its twin for the fisheye lens model"""
     c = _ctx(ctx)
     a = np.asarray(frame)
     if a.dtype != np.uint8:
@@ -764,8 +799,8 @@ def undistort(frame, K, dist, newK=None, ctx=None):
     K, d, n = _camera(K, dist, newK)
     out = np.empty(a.shape, np.uint8)
     h, w = a.shape[:2]
-    check(lib().slam_undistort(c, ptr(a), w, h, a.strides[0], ch, ptr(K), ptr(d), d.size, ptr(n), ptr(out),
-                               out.strides[0]), c)
+    check(_entry("undistort", fisheye)(c, ptr(a), w, h, a.strides[0], ch, ptr(K), ptr(d), d.size, ptr(n), ptr(out),
+                                        out.strides[0]), c)
     return out
 
 
@@ -777,6 +812,11 @@ def undistortBatch(frames, K, dist, newK=None, ctx=None, out=None, stream=None):
     itself; by default the launch goes to the context's stream, after what
     torch's current stream holds so far (the frames' producer) and before what
     it is given later (the result's consumers), both by device-side waits."""
+    return _undistortBatch(False, frames, K, dist, newK, ctx, out, stream)
+
+
+def _undistortBatch(fisheye, frames, K, dist, newK, ctx, out, stream):
+    """undistortBatch, or its twin for the fisheye lens model"""
     import torch
     ctx = ctx or default_context()
     if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or (frames.dim() == 4 and frames.shape[3] != 3):
@@ -798,9 +838,9 @@ def undistortBatch(frames, K, dist, newK=None, ctx=None, out=None, stream=None):
         ready.record(cur)
         torch.cuda.ExternalStream(lib().slam_context_stream(ctx.handle), device=frames.device).wait_event(ready)
     nf, h, w = frames.shape[:3]
-    check(lib().slam_undistort_batch(ctx.handle, None if own else stream, ctypes.c_void_p(frames.data_ptr()),
-                                     ctypes.c_void_p(out.data_ptr()), int(nf), int(w), int(h),
-                                     1 if frames.dim() == 3 else 3, ptr(K), ptr(d), d.size, ptr(n)), ctx.handle)
+    check(_entry("undistort_batch", fisheye)(ctx.handle, None if own else stream, ctypes.c_void_p(frames.data_ptr()),
+                                              ctypes.c_void_p(out.data_ptr()), int(nf), int(w), int(h),
+                                              1 if frames.dim() == 3 else 3, ptr(K), ptr(d), d.size, ptr(n)), ctx.handle)
     if own:
         check(lib().slam_order_after(ctx.handle, ctypes.c_void_p(cur.cuda_stream), None), ctx.handle)
     return out
@@ -819,6 +859,11 @@ def undistortPoints(pts_or_keypoints, K, dist, P=None, criteria=(5, 0.0), ctx=No
     distance in pixels between each input point and the distortion model of its
     result.  A point beyond the fold of the lens model has no preimage: test
     err <= tol before using xy (a NaN fails the test)."""
+    return _undistortPoints(False, pts_or_keypoints, K, dist, P, criteria, ctx)
+
+
+def _undistortPoints(fisheye, pts_or_keypoints, K, dist, P, criteria, ctx):
+    """undistortPoints, or its twin for the fisheye lens model"""
     c = _ctx(ctx)
     a = np.asarray(pts_or_keypoints)
     if a.dtype == KEYPOINT_DTYPE:
@@ -832,9 +877,41 @@ def undistortPoints(pts_or_keypoints, K, dist, P=None, criteria=(5, 0.0), ctx=No
     n = len(a)
     xy = np.empty((n, 2), np.float32)
     err = np.empty(n, np.float32)
-    check(lib().slam_undistort_points(c, ptr(a), stride, n, ptr(K), ptr(d), d.size, ptr(p), int(max_iter), float(eps),
-                                      ptr(xy), ptr(err)), c)
+    check(_entry("undistort_points", fisheye)(c, ptr(a), stride, n, ptr(K), ptr(d), d.size, ptr(p), int(max_iter),
+                                               float(eps), ptr(xy), ptr(err)), c)
     return xy, err
+
+
+# ---- the fisheye lens model (cv::fisheye) -------------------
+
+def fisheyeUndistortMap(w, h, K, dist, newK=None, ctx=None):
+    """undistortMap for the fisheye model (slam_fisheye_undistort_map): the map
+    of cv::fisheye::initUndistortRectifyMap(K, dist, I, newK, (w, h), CV_16SC2),
+    which cv::fisheye::undistortImage builds.  dist: exactly k1 k2 k3 k4; the last
+    row of newK (K when None) is (0, 0, 1)."""
+    return _undistortMap(True, w, h, K, dist, newK, ctx)
+
+
+def fisheyeUndistort(frame, K, dist, newK=None, ctx=None):
+    """cv::fisheye::undistortImage(frame, out, K, dist, newK) of a host frame
+    (slam_fisheye_undistort); otherwise as undistort"""
+    return _undistort(True, frame, K, dist, newK, ctx)
+
+
+def fisheyeUndistortBatch(frames, K, dist, newK=None, ctx=None, out=None, stream=None):
+    """cv::fisheye::undistortImage of n resident frames in one launch
+    (slam_fisheye_undistort_batch); otherwise as undistortBatch"""
+    return _undistortBatch(True, frames, K, dist, newK, ctx, out, stream)
+
+
+def fisheyeUndistortPoints(pts_or_keypoints, K, dist, P=None, criteria=(10, 1e-8), ctx=None):
+    """cv::fisheye::undistortPoints(src, dst, K, dist, noArray(), P, criteria)
+    (slam_fisheye_undistort_points): (xy float32 n x 2, err float32 n).  A point
+    that did not converge under an eps criterion, or whose angle changed sign, is
+    (-1000000, -1000000) as OpenCV writes it, and its err is NaN; otherwise err
+    is the pixel distance between the input and the forward model of the result.
+    Arguments as undistortPoints."""
+    return _undistortPoints(True, pts_or_keypoints, K, dist, P, criteria, ctx)
 
 
 # ---- chessboard calibration (the reference's "calibrate" mode) -------------------
@@ -894,28 +971,45 @@ def chessCandidates(frame, ctx=None):
     return out[:n.value].copy(), s.value
 
 
-def labelChessboard(cand, scale, patternSize):
+def _labeller(name):
+    if name not in ("peel", "grow"):
+        raise ValueError('labeller: "peel" or "grow"')
+    return lib().slam_label_chessboard_grow if name == "grow" else lib().slam_label_chessboard
+
+
+def labelChessboard(cand, scale, patternSize, labeller="peel"):
     """slam_label_chessboard (host only): the patternSize[0] * patternSize[1]
     strongest candidates as a complete board -> (found, corners (n, 2) float32 in
-    full-resolution pixels, canonical order) or (False, None)."""
+    full-resolution pixels, canonical order) or (False, None).  labeller="grow"
+    (slam_label_chessboard_grow): a lattice grown among twice as many candidates,
+    for boards a fisheye lens bends and scenes with clutter stronger than a corner."""
+    label = _labeller(labeller)
     bw, bh = int(patternSize[0]), int(patternSize[1])
     cand = np.ascontiguousarray(cand, np.int32).reshape(-1, 3)
     corners = np.empty((bw * bh, 2), np.float32)
     found = ctypes.c_int(0)
-    check(lib().slam_label_chessboard(ptr(cand), len(cand), int(scale), bw, bh, ptr(corners), ctypes.byref(found)))
+    check(label(ptr(cand), len(cand), int(scale), bw, bh, ptr(corners), ctypes.byref(found)))
     return (True, corners) if found.value else (False, None)
 
 
-def findChessboardCorners(frame, patternSize, ctx=None):
+def findChessboardCorners(frame, patternSize, ctx=None, labeller="peel"):
     """findChessboardCorners(gray, patternSize, corners) (cameraCalibration.cpp:168)
     by this library's own detector: (found, corners) with corners (w * h, 2) float32
     in pixels, row-major with rows of patternSize[0], right-handed in image
     coordinates, first corner nearest the image's origin; (False, None) when the
     strongest candidates are not a complete board.  A resident torch batch
-    (n, h, w[, 3]) gives a list of n such pairs (slam_find_chessboard_dev)."""
+    (n, h, w[, 3]) gives a list of n such pairs (slam_find_chessboard_dev).
+    labeller="grow": the candidates of chessCandidates labelled by
+    labelChessboard(..., labeller="grow")."""
     ctx = ctx or default_context()
     c = ctx.handle
     bw, bh = int(patternSize[0]), int(patternSize[1])
+    if labeller != "peel":
+        _labeller(labeller)
+        cand, s = chessCandidates(frame, ctx=ctx)
+        if isinstance(cand, list):
+            return [labelChessboard(k, s, patternSize, labeller) for k in cand]
+        return labelChessboard(cand, s, patternSize, labeller)
     if not isinstance(frame, np.ndarray) and hasattr(frame, "data_ptr"):
         fr, n, w, h, ch = _resident(frame)
         corners = np.empty((n, bw * bh, 2), np.float32)
@@ -1054,6 +1148,11 @@ def calibrateCamera(objectPoints, imagePoints, imageSize):
     board for all views; imagePoints: (nviews, npts, 2); imageSize (width, height)
     only places the initial principal point.  Returns (rms, K 3x3, D (5,), rvecs
     (nviews, 3), tvecs (nviews, 3))."""
+    return _calibrateCamera(False, objectPoints, imagePoints, imageSize)
+
+
+def _calibrateCamera(fisheye, objectPoints, imagePoints, imageSize):
+    """calibrateCamera, or its twin for the fisheye lens model"""
     obj = np.ascontiguousarray(objectPoints, np.float32)
     if obj.ndim == 3:
         if any(not np.array_equal(o, obj[0]) for o in obj):
@@ -1063,19 +1162,29 @@ def calibrateCamera(objectPoints, imagePoints, imageSize):
     if obj.ndim != 2 or obj.shape[1] != 3 or img.ndim != 3 or img.shape[1:] != (len(obj), 2):
         raise ValueError("objectPoints (npts, 3), imagePoints (nviews, npts, 2)")
     nv = len(img)
-    K, D = np.zeros((3, 3)), np.zeros(5)
+    K, D = np.zeros((3, 3)), np.zeros(4 if fisheye else 5)
     rv, tv = np.zeros((nv, 3)), np.zeros((nv, 3))
     rms = ctypes.c_double(0)
     it = ctypes.c_int(0)
-    check(lib().slam_calibrate_camera(ptr(obj), ptr(img), nv, len(obj), int(imageSize[0]), int(imageSize[1]), ptr(K),
-                                      ptr(D), ptr(rv), ptr(tv), ctypes.byref(rms), ctypes.byref(it)))
+    solve = lib().slam_fisheye_calibrate if fisheye else lib().slam_calibrate_camera
+    check(solve(ptr(obj), ptr(img), nv, len(obj), int(imageSize[0]), int(imageSize[1]), ptr(K), ptr(D), ptr(rv), ptr(tv),
+                ctypes.byref(rms), ctypes.byref(it)))
     return rms.value, K, D, rv, tv
 
 
-def save_calibration(path, K, D, R, T):
+def fisheyeCalibrate(objectPoints, imagePoints, imageSize):
+    """cv::fisheye::calibrate(objectPoints, imagePoints, imageSize, K, D, R, T) with
+    the skew fixed at 0 (slam_fisheye_calibrate), on the host in f64: the optimum
+    over fx fy cx cy, k1 k2 k3 k4 and a pose per view.  Arguments and result as
+    calibrateCamera, with D (4,)."""
+    return _calibrateCamera(True, objectPoints, imagePoints, imageSize)
+
+
+def save_calibration(path, K, D, R, T, model=None):
     """saveCalibParametersToXML (IOmisc.cpp:68-76): K 3x3 "d", DC 1x5 "d", R and T
     Nx1 "3d" in OpenCV's XML storage, doubles as %.16e: load_calibration reads each
-    key back bit for bit."""
+    key back bit for bit.  model="fisheye": DC is k1 k2 k3 k4 of cv::fisheye and
+    the file carries the string node <model>fisheye</model> that says so."""
     def node(name, rows, cols, dt, data):
         vals = " ".join("%.16e" % float(v) for v in np.asarray(data, np.float64).ravel())
         return (f'<{name} type_id="opencv-matrix">\n  <rows>{rows}</rows>\n  <cols>{cols}</cols>\n'
@@ -1086,7 +1195,10 @@ def save_calibration(path, K, D, R, T):
     T = np.asarray(T, np.float64).reshape(-1, 3)
     if len(R) != len(T):
         raise ValueError("one rotation and one translation per view")
-    text = ('<?xml version="1.0"?>\n<opencv_storage>\n' + node("K", 3, 3, "d", K) + node("DC", 1, D.size, "d", D) +
+    if model not in (None, "fisheye") or (model == "fisheye" and D.size != 4):
+        raise ValueError('model: None, or "fisheye" with four coefficients')
+    name = "" if model is None else f"<model>{model}</model>\n"
+    text = ('<?xml version="1.0"?>\n<opencv_storage>\n' + name + node("K", 3, 3, "d", K) + node("DC", 1, D.size, "d", D) +
             node("R", len(R), 1, '"3d"', R) + node("T", len(T), 1, '"3d"', T) + "</opencv_storage>\n")
     with open(path, "w") as f:
         f.write(text)

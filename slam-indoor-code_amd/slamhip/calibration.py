@@ -3,8 +3,11 @@ chessboardPhotosCalibration, cameraCalibration.cpp:14-32, 142-203) on the device
 findChessboardCorners -> cornerSubPix over resident frames, calibrateCamera on the
 host, saveCalibParametersToXML.
 
+model="fisheye" (opt-in; DESIGN.md section 19) calibrates cv::fisheye's lens model
+instead: the growing labeller finds the bent boards, fisheyeCalibrate solves.
+
 Out of scope: the video and webcam branches (no video decode), the preview window
-and drawChessboardCorners (visualCalibration is ignored), the fisheye model.
+and drawChessboardCorners (visualCalibration is ignored).
 """
 import glob
 import os
@@ -18,6 +21,7 @@ from .config import ConfigService
 MINIMAL_FOUND_FRAMES_COUNT = 10      # cameraCalibration.h
 SUBPIX_WIN = (11, 11)                # cameraCalibration.cpp:169-170
 SUBPIX_CRITERIA = (30, 1e-4)
+FISHEYE_SUBPIX_WIN = (5, 5)          # a fisheye photo's squares are a few pixels wide near the rim
 
 
 class CalibrationError(RuntimeError):
@@ -55,8 +59,9 @@ class DeviceOps:
     batch of equally sized frames, cornerSubPix per found board on the same
     resident frame"""
 
-    def __init__(self, ctx=None):
+    def __init__(self, ctx=None, labeller="peel", subpix_win=SUBPIX_WIN):
         self.ctx = ctx or api.default_context()
+        self.labeller, self.subpix_win = labeller, tuple(subpix_win)
 
     def detect(self, frames, board_size):
         import torch
@@ -68,17 +73,17 @@ class DeviceOps:
             while e < len(frames) and frames[e].shape == frames[k].shape:
                 e += 1
             batch = torch.from_numpy(np.stack(frames[k:e])).to(dev)
-            found = api.findChessboardCorners(batch, board_size, ctx=self.ctx)
+            found = api.findChessboardCorners(batch, board_size, ctx=self.ctx, labeller=self.labeller)
             for f, (ok, corners) in enumerate(found):
                 if ok:
-                    corners = api.cornerSubPix(batch[f], corners, SUBPIX_WIN, SUBPIX_CRITERIA, ctx=self.ctx)
+                    corners = api.cornerSubPix(batch[f], corners, self.subpix_win, SUBPIX_CRITERIA, ctx=self.ctx)
                 out[k + f] = (ok, corners)
             k = e
         return out
 
 
 def chessboard_photos_calibration(frames_or_paths, iters_count=10, square_size=23.0, board_size=(7, 7), ops=None,
-                                  ctx=None, with_corners=False, decoder=None):
+                                  ctx=None, with_corners=False, decoder=None, model=None, subpix_win=None):
     """chessboardPhotosCalibration (cameraCalibration.cpp:142-203): frames (arrays or
     paths) are examined in order; empty frames and frames without a board are
     skipped; the search stops at iters_count boards; fewer than 10
@@ -87,10 +92,17 @@ def chessboard_photos_calibration(frames_or_paths, iters_count=10, square_size=2
     ops: an object with detect(frames, board_size) -> [(found, refined corners)]
     (default: DeviceOps(ctx)).  decoder: None = read_frame (PIL on the host);
     "gpu" = paths ending in .jpg / .jpeg are decoded on the device (api.imread,
-    byte-identical to cv::imread on baseline JPEG); other paths go to read_frame."""
+    byte-identical to cv::imread on baseline JPEG); other paths go to read_frame.
+    model="fisheye": the boards are labelled by the growing labeller, refined in
+    subpix_win (default (5, 5); (11, 11) for the default model) and the camera is
+    that of api.fisheyeCalibrate, D = k1 k2 k3 k4, from Size(cols, rows)."""
     if decoder not in (None, "gpu"):
         raise ValueError("decoder is None or 'gpu'")
-    ops = ops or DeviceOps(ctx)
+    if model not in (None, "fisheye"):
+        raise ValueError('model is None or "fisheye"')
+    fisheye = model == "fisheye"
+    win = subpix_win or (FISHEYE_SUBPIX_WIN if fisheye else SUBPIX_WIN)
+    ops = ops or DeviceOps(ctx, "grow" if fisheye else "peel", win)
     obj = object_points(board_size, square_size)
     image_points = []
     last = None
@@ -125,7 +137,10 @@ def chessboard_photos_calibration(frames_or_paths, iters_count=10, square_size=2
     # so the quirk moves the start of the search, not the optimum; it is kept as it is.
     rows, cols = last.shape[:2]
     pts = np.stack(image_points)
-    rms, K, D, R, T = api.calibrateCamera(obj, pts, (rows, cols))
+    if fisheye:
+        rms, K, D, R, T = api.fisheyeCalibrate(obj, pts, (cols, rows))
+    else:
+        rms, K, D, R, T = api.calibrateCamera(obj, pts, (rows, cols))
     return (rms, K, D, R, T, pts) if with_corners else (rms, K, D, R, T)
 
 

@@ -202,13 +202,16 @@ class GpuOps:
         r.dev = dev
         return r
 
-    def undistort(self, frame, K, dist, newK=None):
+    def undistort(self, frame, K, dist, newK=None, lens_model=None):
         """cv::undistort of a frame at the batch.cpp:244 seam, on its resident
         copy (slam_undistort_batch): a ResidentFrame whose host pixels (the point
         colours are read from them) and HBM copy are the undistorted ones.
         Frames the device batch path does not take (not BGR) go through the
-        host-buffer entry point."""
-        from .api import undistort, undistortBatch
+        host-buffer entry point.  lens_model="fisheye": cv::fisheye::undistortImage."""
+        from . import api
+        fisheye = _is_fisheye(lens_model)
+        undistort = api.fisheyeUndistort if fisheye else api.undistort
+        undistortBatch = api.fisheyeUndistortBatch if fisheye else api.undistortBatch
         frame = self.ingest(frame)
         dev = getattr(frame, "dev", None)
         if dev is None:
@@ -218,13 +221,14 @@ class GpuOps:
         r.dev = out
         return r
 
-    def undistort_points(self, kps, K, dist, P=None, criteria=(5, 0.0)):
+    def undistort_points(self, kps, K, dist, P=None, criteria=(5, 0.0), lens_model=None):
         """cv::undistortPoints of a keypoint record array, its .pt read in place
         at the record stride (slam_undistort_points): (xy float32 n x 2, err
         float32 n).  Runs on the search context: call it from the thread that
-        runs the searches."""
-        from .api import undistortPoints
-        return undistortPoints(np.ascontiguousarray(kps, KEYPOINT_DTYPE), K, dist, P, criteria, ctx=self.ctx)
+        runs the searches.  lens_model="fisheye": cv::fisheye::undistortPoints."""
+        from . import api
+        points = api.fisheyeUndistortPoints if _is_fisheye(lens_model) else api.undistortPoints
+        return points(np.ascontiguousarray(kps, KEYPOINT_DTYPE), K, dist, P, criteria, ctx=self.ctx)
 
     def _batches(self):
         if self._db is None:
@@ -694,6 +698,19 @@ class JpegMedia:
         return f[0] if f else None
 
 
+def _is_fisheye(lens_model):
+    """lens_model: None (the Brown-Conrady polynomial of cv::undistort) or "fisheye" (cv::fisheye)"""
+    if lens_model not in (None, "fisheye"):
+        raise ValueError('lens_model: None or "fisheye"')
+    return lens_model == "fisheye"
+
+
+def _lens_kw(lens_model):
+    """the keyword an ops method is given for a lens model: none for the default
+    one, so ops written before the fisheye model keep working"""
+    return {"lens_model": lens_model} if _is_fisheye(lens_model) else {}
+
+
 class UndistortedMedia:
     """Any media with cv::undistort(frame, K, dist, newK) applied where the
     reference marks the seam (batch.cpp:244, between getNextFrame and
@@ -701,16 +718,19 @@ class UndistortedMedia:
     Over a DeviceMedia the whole resident sequence is undistorted in one
     slam_undistort_batch and the frames handed out are views of the result, so a
     batch's frames stay one contiguous range and take(n) keeps working (the
-    attribute exists only then: fillVideoFrameBatch tests for it)."""
+    attribute exists only then: fillVideoFrameBatch tests for it).
+    lens_model="fisheye": cv::fisheye::undistortImage(frame, K, dist, newK)."""
 
-    def __init__(self, media, K, dist, ops, newK=None):
+    def __init__(self, media, K, dist, ops, newK=None, lens_model=None):
         self.media, self.ops = media, ops
+        self.lens = _lens_kw(lens_model)
         self.K = np.array(K, np.float64)     # a copy: BA refines the pipeline's K in place
         self.dist = np.array(dist, np.float64).reshape(-1)
         self.newK = None if newK is None else np.array(newK, np.float64)
         self._seq = None
         if isinstance(media, DeviceMedia):
-            from .api import undistortBatch
+            from . import api
+            undistortBatch = api.fisheyeUndistortBatch if self.lens else api.undistortBatch
             rest = media.dev[media.i:]
             dev = undistortBatch(rest, self.K, self.dist, self.newK, ctx=ops.ctx)
             host = dev.cpu().numpy() if media.host is not None else None
@@ -724,7 +744,7 @@ class UndistortedMedia:
         f = self.media.next_frame()
         if f is None:
             return None
-        return self.ops.undistort(f, self.K, self.dist, self.newK)
+        return self.ops.undistort(f, self.K, self.dist, self.newK, **self.lens)
 
 
 class MediaSources:
@@ -755,10 +775,13 @@ class PointLens:
     ops.undistort_points) instead of the frames.  lens(kps) is (xy float32
     n x 2 in the pixels of P, valid bool n); a keypoint whose residual exceeds
     max_residual pixels (or is NaN) has no undistorted position: it lies beyond
-    the fold of the lens model, or the iteration did not reach it."""
+    the fold of the lens model, or the iteration did not reach it.
+    lens_model="fisheye": cv::fisheye::undistortPoints, whose rejected points
+    (a NaN residual) have no undistorted position either."""
 
-    def __init__(self, ops, K, dist, P, criteria, max_residual):
+    def __init__(self, ops, K, dist, P, criteria, max_residual, lens_model=None):
         self.ops = ops
+        self.lens = _lens_kw(lens_model)
         self.K = np.array(K, np.float64)       # copies: BA refines the pipeline's K in place
         self.dist = np.array(dist, np.float64).reshape(-1)
         self.P = np.array(P, np.float64)
@@ -766,7 +789,7 @@ class PointLens:
         self.max_residual = float(max_residual)
 
     def __call__(self, kps):
-        xy, err = self.ops.undistort_points(kps, self.K, self.dist, self.P, self.criteria)
+        xy, err = self.ops.undistort_points(kps, self.K, self.dist, self.P, self.criteria, **self.lens)
         return xy, err <= np.float32(self.max_residual)
 
 
@@ -1398,7 +1421,7 @@ def define_camera_position(old_deque, last_id, fd):
 
 
 def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK=None, undistort="frames",
-              criteria=(50, 0.01), max_residual=0.01, tracker=None, klt=None):
+              criteria=(50, 0.01), max_residual=0.01, tracker=None, klt=None, lens_model=None):
     """src/main.cpp:71-107 slamMain: mainCycle restarts from the last pose until
     the sequence ends, then points.txt / colors.txt.  K (3x3 float64) is
     updated in place by BA, as the reference's calibrationMatrix is.  dist: the
@@ -1418,6 +1441,12 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
     coordinates; the point colours are read from the raw frame at the raw
     coordinates, the same physical pixel.
 
+    lens_model="fisheye" (opt-in; None is the polynomial model above) reads dist
+    as the four coefficients k1 k2 k3 k4 of cv::fisheye: "frames" undistorts with
+    cv::fisheye::undistortImage, "points" with cv::fisheye::undistortPoints, where
+    eps of `criteria` bounds the last Newton step of the angle instead of a
+    pixel error and a point OpenCV rejects has no undistorted position.
+
     tracker="klt" (opt-in; the reference's useFeatureTracker mode) searches
     without descriptors: the previous good frame's feature positions are tracked
     into every candidate by cv::calcOpticalFlowPyrLK with the arguments in `klt`
@@ -1433,13 +1462,16 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
         raise ValueError('tracker: None or "klt"')
     if tracker is not None and dist is not None:
         raise ValueError("tracker together with dist is not supported")
+    if _is_fisheye(lens_model) and (dist is None or np.size(dist) != 4):
+        raise ValueError('lens_model="fisheye" takes the four coefficients k1 k2 k3 k4 as dist')
     ops = ops or GpuOps()
     lens = None
-    if dist is not None and np.any(np.asarray(dist, np.float64) != 0):
+    # all-zero coefficients are no lens at all in the polynomial model; in the fisheye model they are the equidistant lens
+    if dist is not None and (_is_fisheye(lens_model) or np.any(np.asarray(dist, np.float64) != 0)):
         if undistort == "frames":
-            media = UndistortedMedia(media, K, dist, ops, newK)
+            media = UndistortedMedia(media, K, dist, ops, newK, lens_model)
         else:
-            lens = PointLens(ops, K, dist, K if newK is None else newK, criteria, max_residual)
+            lens = PointLens(ops, K, dist, K if newK is None else newK, criteria, max_residual, lens_model)
     cond = Conditions(cfg)
     if tracker is not None:
         cond.tracker = klt or KltParams()
