@@ -828,6 +828,80 @@ int slam_jpeg_last_orientations(slam_ctx* ctx, int32_t* out, int n);
  * bytes uploaded, 1 table + segment bytes uploaded, 2 coefficient bytes, 3 frame bytes written */
 int slam_jpeg_last_timing(slam_ctx* ctx, double* ms5, uint64_t* bytes4);
 
+/* ---- Motion-JPEG: the two stream rules, and chunk-parallel entropy decoding ------ */
+/* Parse flags of the _ex entry points (the calls above take none).  SLAM_JPEG_MJPEG:
+ * the stream is a frame of a Motion-JPEG video, read as OpenCV's CAP_OPENCV_MJPEG
+ * backend and libjpeg read it: an undefined Huffman table slot 0 or 1 is the Annex K
+ * table of its class (AVI frames usually carry no DHT; slots 2 and 3 stay undefined),
+ * and a frame whose AVI1 APP0 says it is one field of an interlaced pair is
+ * SLAM_E_UNSUPPORTED (polarity 0, a progressive frame, is taken).  Unknown flag bits:
+ * SLAM_E_INVALID_ARG. */
+enum slam_jpeg_flags { SLAM_JPEG_MJPEG = 1 };
+int slam_jpeg_info_ex(const uint8_t* buf, size_t len, struct slam_jpeg_info* out, int flags);
+int slam_jpeg_decode_host_ex(const uint8_t* buf, size_t len, uint8_t* out, size_t step, int channels, int flags,
+                             int* status);
+int slam_jpeg_decode_batch_dev_ex(slam_ctx* ctx, void* stream, const uint8_t* const* bufs, const size_t* lens, int n,
+                                  int w, int h, uint8_t* d_frames, int* status, int flags);
+/* the Annex K table of a class (0 DC, 1 AC) and slot (0 luminance, 1 chrominance):
+ * counts16[16] codes per length, the values (vals256: room for 256) and their number */
+int slam_jpeg_std_table(int klass, int slot, uint8_t* counts16, uint8_t* vals256, int* nvals);
+
+/* Chunk-parallel entropy decoding (SLAM_OPT_JPEG_SYNC, jpeg_huff.h): a segment
+ * without restart markers is decoded by one lane per chunk of its bytes instead of
+ * one lane in all: speculative decoding from every chunk start that synchronises
+ * with the true symbol sequence (rounds inside a workgroup of `lanes` chunks, then a
+ * fixed number of launches that pass states between workgroups), a verified count
+ * of blocks and DC sums per chunk, a scan, and a write pass through the serial
+ * decoder's own block function.  The result of a stream is by definition the serial
+ * decoder's: a segment whose chain of states does not verify, that meets a fault
+ * or whose block count is not the expected one is cleared and decoded serially. */
+struct slam_jpeg_sync_stats {
+    int32_t parallel_segments;     /* segments that took the parallel path */
+    int32_t fallback_segments;     /* ... of which were decoded serially after all */
+    int32_t chunk_bytes, lanes;    /* the geometry: bytes per chunk, chunks per workgroup */
+    int64_t chunks;                /* chunks of the parallel segments */
+    int32_t wg_rounds_max;         /* rounds inside a workgroup: the most any workgroup needed in a launch */
+    int32_t launch_rounds_max;     /* launches in which a segment still changed: the most any segment needed */
+    int64_t wg_rounds_total;       /* ... summed over workgroups and launches */
+    int64_t launch_rounds_total;   /* ... summed over segments */
+    double ms[5];                  /* device only: jpeg_sync (all launches), jpeg_sync_count, jpeg_sync_scan,
+                                      jpeg_sync_write, the fall-back (clear + jpeg_huff); 0 from the host driver */
+};
+/* of the context's last slam_jpeg_decode_batch_dev[_ex] (all zero when SLAM_OPT_JPEG_SYNC was 0) */
+int slam_jpeg_last_sync(slam_ctx* ctx, struct slam_jpeg_sync_stats* stats);
+/* slam_jpeg_decode_host_ex with every segment of more than one chunk on the
+ * parallel path (SLAM_OPT_JPEG_SYNC = 2), run on the host by the functions the
+ * kernels share, in their round structure and geometry: pixels and status are
+ * slam_jpeg_decode_host_ex's, and stats (nullable) are what the device reports for
+ * the same stream.  chunk_bytes: 0 = the default, or a power of two from 16 to 1024. */
+int slam_jpeg_decode_host_sync(const uint8_t* buf, size_t len, uint8_t* out, size_t step, int channels,
+                               int chunk_bytes, int flags, int* status, struct slam_jpeg_sync_stats* stats);
+
+/* ---- Motion-JPEG AVI container (avi_parse.cpp): host only ----------------------- */
+/* The frames of the first video stream of an AVI file held in memory, found by
+ * walking the chunks: every top-level RIFF (AVI and OpenDML AVIX), LIST hdrl (avih,
+ * the first strl whose strh is 'vids', its strf BITMAPINFOHEADER), every LIST movi
+ * and nested LIST rec; the NNdc / NNdb chunks of that stream in file order.  Other
+ * streams, JUNK and every index (idx1, indx, ixNN) are skipped: the walk is the
+ * definition (OpenCV trusts idx1; the two agree on well-formed files).  A video
+ * chunk of no bytes is a dropped frame and repeats the one before it (a first
+ * frame of no bytes stays empty).  offsets / sizes (nullable, cap entries): the
+ * frames' byte ranges in buf; info->frames is the number found, also beyond cap.
+ * SLAM_E_UNSUPPORTED: no video stream, or a codec other than MJPG (any letter case)
+ * or jpeg.  SLAM_E_INVALID_ARG: not RIFF / AVI, a chunk or list that runs past its
+ * parent or the buffer, no hdrl.  slam_avi_last_error: the message of the calling
+ * thread's last failing slam_avi_index. */
+struct slam_avi_info {
+    int32_t width, height;
+    uint32_t rate, scale;          /* frames per second = rate / scale */
+    int64_t frames;
+    uint32_t handler, compression; /* FourCCs (little endian): strh's fccHandler, strf's biCompression */
+    int32_t stream;                /* the stream's number NN */
+};
+const char* slam_avi_last_error(void);
+int slam_avi_index(const uint8_t* buf, size_t len, struct slam_avi_info* info, uint64_t* offsets, uint64_t* sizes,
+                   size_t cap);
+
 /* ---- scene rendering (the cv::viz window of vizualizePointsAndCameras, headless) -- */
 /* A deterministic z-buffer rasteriser for the onlyViz scene: the coloured cloud
  * (WCloud: n_pts x 3 f32 points, n_pts x 3 u8 BGR colours), the meshes (WMesh:
@@ -896,7 +970,11 @@ int slam_render_last_stats(slam_ctx* ctx, uint64_t* stats, double* ms);
  * four part-walks (the tests' way to run those paths on every keypoint).
  * Unknown option or value: SLAM_E_INVALID_ARG. */
 enum slam_option { SLAM_OPT_SIFT_KERNEL = 1, SLAM_OPT_SIFT_BAND_SPLIT = 2, SLAM_OPT_PNP_SUMS = 3,
-                   SLAM_OPT_FAST_REUSE = 4, SLAM_OPT_JPEG_LANES = 5 };
+                   SLAM_OPT_FAST_REUSE = 4, SLAM_OPT_JPEG_LANES = 5, SLAM_OPT_JPEG_SYNC = 6, SLAM_OPT_JPEG_CHUNK = 7 };
+/* SLAM_OPT_JPEG_SYNC: which segments of a batch decode take the chunk-parallel path
+ * (slam_jpeg_sync_stats above): 0 (default) = none, 1 = those of at least 16384
+ * bytes, 2 = every one of more than one chunk (for tests).  SLAM_OPT_JPEG_CHUNK: bytes
+ * per chunk, a power of two from 16 to 1024; 0 (default) = 256.  Neither changes results. */
 /* SLAM_OPT_JPEG_LANES: how many lanes of a wave of jpeg_huff take a segment each
  * (1 .. 64); 0 (default) = one per wave until the device's wave slots are full,
  * then as many as the segment count needs.  Never changes results. */

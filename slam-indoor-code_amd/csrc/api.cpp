@@ -423,7 +423,7 @@ void slam_destroy(slam_ctx* c)
                       &c->undist_xy, &c->undist_frac, &c->undist_out, &c->undist_pts,
                       &c->calib_resp, &c->calib_mask, &c->calib_out, &c->calib_sub,
                       &c->klt_img, &c->klt_pyr, &c->klt_deriv, &c->klt_pts,
-                      &c->jpeg_in, &c->jpeg_coef, &c->jpeg_planes, &c->jpeg_out,
+                      &c->jpeg_in, &c->jpeg_coef, &c->jpeg_planes, &c->jpeg_out, &c->jpeg_sync,
                       &c->render_ws, &c->render_in, &c->render_out};
     for (DevBuf* b : bufs) b->release();
     if (c->h_up) (void)hipHostFree(c->h_up);
@@ -2048,6 +2048,15 @@ int slam_set_option(slam_ctx* c, int option, int value)
     case SLAM_OPT_JPEG_LANES:
         if (value < 0 || value > 64) return set_err(c, SLAM_E_INVALID_ARG, "SLAM_OPT_JPEG_LANES takes 0 (auto) .. 64");
         c->opt_jpeg_lanes = value;
+        return SLAM_OK;
+    case SLAM_OPT_JPEG_SYNC:
+        if (value < 0 || value > 2) return set_err(c, SLAM_E_INVALID_ARG, "SLAM_OPT_JPEG_SYNC takes 0 (off), 1 (auto) or 2 (all)");
+        c->opt_jpeg_sync = value;
+        return SLAM_OK;
+    case SLAM_OPT_JPEG_CHUNK:
+        if (value != 0 && (value < 16 || value > 1024 || (value & (value - 1))))
+            return set_err(c, SLAM_E_INVALID_ARG, "SLAM_OPT_JPEG_CHUNK takes 0 (default) or a power of two from 16 to 1024");
+        c->opt_jpeg_chunk = value;
         return SLAM_OK;
     default:
         return set_err(c, SLAM_E_INVALID_ARG, "unknown option");

@@ -1,9 +1,11 @@
 // Baseline JPEG entropy decoding (libjpeg's jdhuff.c restated), host and device,
 // header only: the bit reader, the Huffman table build and lookup, and the
 // decoding of one block and of one segment (a restart interval, or the whole scan
-// of a stream without DRI).  jpeg.hip's jpeg_huff kernel and the host decoder
-// (jpeg_parse.cpp) call the same functions; tests/cpp/jpeg_fuzz_test.cpp runs them
-// under the address and undefined-behaviour sanitizers.
+// of a stream without DRI), and the per-chunk steps of the chunk-parallel decoding
+// of one segment (below).  jpeg.hip's kernels and the host decoders
+// (jpeg_parse.cpp) call the same functions; tests/cpp/jpeg_fuzz_test.cpp and
+// tests/cpp/mjpeg_fuzz_test.cpp run them under the address and undefined-behaviour
+// sanitizers.
 //
 // Bounds.  The reader never touches a byte at or past the segment's end: past it
 // it supplies zero bits and counts them.  Every table index is masked or checked
@@ -129,8 +131,9 @@ struct BitReader {
     JPEG_HD bool overrun() const { return pad > (uint32_t)n; }
 };
 
-// the next symbol, or -1 when the 16 bits ahead start no code
-JPEG_HD inline int huff_decode(BitReader& br, const HuffTable& t)
+// the next symbol, or -1 when the 16 bits ahead start no code (Reader: BitReader or PosReader)
+template <class Reader>
+JPEG_HD inline int huff_decode(Reader& br, const HuffTable& t)
 {
     br.fill();
     const uint32_t b16 = br.peek(16);
@@ -259,6 +262,298 @@ JPEG_HD inline int decode_segment(const ImageDesc& im, const HuffTable* tables, 
             mx = 0;
             my++;
         }
+    }
+    return 0;
+}
+
+// ---- chunk-parallel decoding of one segment ---------------
+//
+// A faster way to decode_segment's bytes, after Weissenberger & Schmidt's
+// self-synchronising decoder; never a second definition: a segment is accepted only
+// when the chain of states below is proven from the segment's true start and every
+// block was decoded by decode_block without a fault, and is otherwise decoded by
+// decode_segment itself.
+//
+// The segment's bytes [off, end) are cut into chunks of C bytes; one lane owns one
+// chunk and the symbols that START in it.  A state is a symbol boundary: (byte, bit)
+// of the next unread bit in the raw stream, the block index inside the MCU and the
+// zigzag position k (0: a DC symbol comes next).  sync_walk decodes from an entry
+// state to the first boundary at or past the chunk's limit and returns that exit
+// state; a lane's entry is its predecessor's exit, or the cold state (chunk start,
+// block 0, k 0) while that is unknown.  The rounds that repeat this until nothing
+// changes are the callers' (jpeg.hip's jpeg_sync kernel and jpeg_parse.cpp's host
+// driver, the same structure); sync_walk with a ChunkCount then verifies the chain
+// (entry = the stored exit of the predecessor, recomputed exit = the stored one) and
+// counts the blocks started and their DC differences per component, modulo 2^32; an
+// exclusive scan gives each chunk its first block index and predictors, and
+// sync_write decodes the chunk's blocks with decode_block into decode_segment's layout.
+//
+// Bounds: every walk is limited to max_steps symbols (a symbol is at least one bit),
+// the readers never touch a byte at or past the segment's end, and sync_write
+// writes only blocks below the segment's block count, at addresses checked against
+// the component's grid.
+constexpr int kSyncLanes = 256;          // chunks of one workgroup (and of the host driver's)
+constexpr int kSyncLaunches = 4;         // rounds between workgroups: one cold launch and three that pass states on
+constexpr int kSyncChunkMin = 16, kSyncChunkMax = 1024;
+constexpr uint64_t kStateUnknown = ~0ull;          // a fault met while speculating: the successor starts cold
+constexpr uint64_t kStateEnd = ~0ull - 1;          // the segment's bytes are used up: the successors have nothing to do
+constexpr uint32_t kChunkFault = 1;      // a fault of the stream itself (met in the verified chain or by decode_block)
+constexpr uint32_t kChunkMismatch = 2;   // the recomputed exit state is not the stored one
+
+JPEG_HD inline uint64_t state_pack(uint32_t byte, int bit, int blk, int k)
+{
+    return ((uint64_t)byte << 32) | ((uint64_t)(bit & 7) << 16) | ((uint64_t)(blk & 255) << 8) | (uint64_t)(k & 255);
+}
+
+// BitReader that also knows where in the raw stream its next unread bit lies.
+// stuff: bit i set when the i-th most recently loaded byte was followed by a skipped 00.
+struct PosReader {
+    const uint8_t* p;
+    uint32_t pos, end;
+    uint32_t acc;
+    int n;
+    uint32_t pad;
+    uint32_t stuff;
+
+    JPEG_HD void init(const uint8_t* base, uint32_t off, uint32_t stop)
+    {
+        p = base;
+        pos = off;
+        end = stop < off ? off : stop;
+        acc = 0;
+        n = 0;
+        pad = 0;
+        stuff = 0;
+    }
+    JPEG_HD void fill()
+    {
+        while (n <= 24) {
+            uint32_t b = 0, st = 0;
+            if (pos < end) {
+                b = p[pos++];
+                if (b == 0xFF && pos < end && p[pos] == 0) {
+                    pos++;
+                    st = 1;
+                }
+            } else {
+                pad += 8;
+            }
+            acc = (acc << 8) | b;
+            stuff = (stuff << 1) | st;
+            n += 8;
+        }
+    }
+    JPEG_HD uint32_t peek(int k) const { return (acc >> (n - k)) & ((1u << k) - 1u); }
+    JPEG_HD void skip(int k) { n -= k; }
+    JPEG_HD bool overrun() const { return pad > (uint32_t)n; }
+    // fewer than 16 bits of the stream are left unread
+    JPEG_HD bool near_end() const { return pos >= end && n - (int)pad < 16; }
+    // the raw byte that holds the next unread bit, and the bit's index in it (0 = the top bit); not after an overrun
+    JPEG_HD void position(uint32_t& byte, int& bit) const
+    {
+        const int real = n - (int)pad;                 // unread bits that came from the stream
+        const int nb = (real + 7) >> 3;                // the loaded bytes they lie in (at most 4)
+        const uint32_t m = (stuff >> (pad >> 3)) & ((1u << nb) - 1u);
+        int skipped = 0;
+        for (int i = 0; i < 4; i++) skipped += (int)((m >> i) & 1u);
+        byte = pos - (uint32_t)nb - (uint32_t)skipped;
+        bit = (8 - (real & 7)) & 7;
+    }
+};
+
+// One segment that takes the parallel path, as both sides read it.
+struct SyncSeg {
+    uint32_t image;
+    uint32_t off, end;       // its bytes in the byte buffer
+    uint32_t mcu0;
+    uint32_t nblocks;        // the blocks decode_segment decodes
+    uint32_t nchunks;
+    uint32_t chunk0;         // its first chunk slot: a multiple of kSyncLanes
+    uint32_t bpm;            // blocks per MCU (at most 10)
+    uint64_t blkinfo;        // 6 bits per block of an MCU: component | DC slot << 2 | AC slot << 4
+};
+
+// What the verified walk of one chunk found.
+struct ChunkCount {
+    uint32_t nstart;         // blocks whose DC symbol starts in the chunk
+    uint32_t dc0, dc1, dc2;  // the sum of their DC differences per component, modulo 2^32
+    uint64_t first;          // the state at the first of them
+    uint32_t flags;          // kChunk*
+};
+
+JPEG_HD inline uint32_t seg_blocks_per_mcu(const ImageDesc& im)
+{
+    uint32_t n = 0;
+    for (int c = 0; c < im.ncomp && c < 3; c++) n += (uint32_t)(im.comp[c].h * im.comp[c].v);
+    return n;
+}
+
+// fills everything but chunk0; false when the segment cannot take the parallel path
+inline bool sync_seg_init(SyncSeg& s, const ImageDesc& im, const Segment& sg, uint32_t chunk_bytes)
+{
+    const uint32_t bpm = seg_blocks_per_mcu(im);
+    if (im.mcus_x < 1 || bpm < 1 || bpm > 10 || sg.end <= sg.off) return false;
+    const uint64_t total = (uint64_t)im.mcus_x * (uint64_t)im.mcus_y;
+    if (sg.mcu0 >= total) return false;
+    const uint64_t nm = total - sg.mcu0 < sg.nmcu ? total - sg.mcu0 : sg.nmcu;
+    if (nm * bpm > 0x7FFFFFFFull) return false;
+    s.image = sg.image;
+    s.off = sg.off;
+    s.end = sg.end;
+    s.mcu0 = sg.mcu0;
+    s.nblocks = (uint32_t)(nm * bpm);
+    s.nchunks = (sg.end - sg.off + chunk_bytes - 1) / chunk_bytes;
+    s.chunk0 = 0;
+    s.bpm = bpm;
+    s.blkinfo = 0;
+    int b = 0;
+    for (int c = 0; c < im.ncomp && c < 3; c++)
+        for (int i = 0; i < im.comp[c].h * im.comp[c].v; i++, b++)
+            s.blkinfo |= (uint64_t)((uint32_t)c | ((uint32_t)(im.comp[c].dc & 3) << 2) | ((uint32_t)(im.comp[c].ac & 3) << 4)) << (6 * b);
+    return true;
+}
+
+// the cold state of chunk ci: its first byte, or the byte after it when that is the 00 of an FF 00 pair
+JPEG_HD inline uint64_t sync_cold(const uint8_t* bytes, const SyncSeg& sg, uint32_t ci, uint32_t chunk_bytes)
+{
+    uint32_t b = sg.off + ci * chunk_bytes;
+    if (ci && bytes[b] == 0 && bytes[b - 1] == 0xFF) b++;
+    return state_pack(b, 0, 0, 0);
+}
+
+// the entry state of a chunk whose predecessor left `prev`
+JPEG_HD inline uint64_t sync_entry(uint64_t prev, uint64_t cold) { return prev == kStateUnknown ? cold : prev; }
+
+// Decodes, without writing, the symbols that start at or after `entry` and before byte `limit`.
+// Returns the exit state.  cc (nullable): counts the blocks started; a fault sets kChunkFault there
+// unless fewer than 16 bits of the segment are left (the padding after the last block, which
+// decode_segment never reads; what it does read is decoded again by sync_write).
+JPEG_HD inline uint64_t sync_walk(const HuffTable* tables, const uint8_t* bytes, const SyncSeg& sg, uint64_t entry,
+                                  uint32_t limit, uint32_t max_steps, ChunkCount* cc)
+{
+    if (cc) {
+        cc->nstart = cc->dc0 = cc->dc1 = cc->dc2 = 0;
+        cc->first = 0;
+        cc->flags = 0;
+    }
+    if (entry == kStateEnd || entry == kStateUnknown) return entry;
+    uint32_t byte = (uint32_t)(entry >> 32);
+    int bit = (int)(entry >> 16) & 7, blk = (int)(entry >> 8) & 255, k = (int)entry & 255;
+    if (byte >= limit) return entry;
+    if (byte < sg.off || blk >= (int)sg.bpm || k > 63) return kStateUnknown;      // never: states are made here
+    PosReader br;
+    br.init(bytes, byte, sg.end);
+    br.fill();
+    br.skip(bit);
+    for (uint32_t step = 0; step < max_steps; step++) {
+        br.fill();
+        br.position(byte, bit);
+        if (byte >= limit) return state_pack(byte, bit, blk, k);
+        const uint32_t info = (uint32_t)(sg.blkinfo >> (6 * blk)) & 63u;
+        bool fault = false;
+        if (k == 0) {
+            const int t = huff_decode(br, tables[(info >> 2) & 3]);
+            int diff = 0;
+            if (t < 0 || t > 16) {
+                fault = true;
+            } else if (t) {
+                br.fill();
+                diff = extend((int)br.peek(t), t);
+                br.skip(t);
+            }
+            if (!fault) {
+                if (br.overrun()) return kStateEnd;
+                if (cc) {
+                    if (!cc->nstart) cc->first = state_pack(byte, bit, blk, 0);
+                    cc->nstart++;
+                    const uint32_t c = info & 3u;
+                    cc->dc0 += c == 0 ? (uint32_t)diff : 0u;
+                    cc->dc1 += c == 1 ? (uint32_t)diff : 0u;
+                    cc->dc2 += c == 2 ? (uint32_t)diff : 0u;
+                }
+                k = 1;
+            }
+        } else {
+            const int rs = huff_decode(br, tables[4 + ((info >> 4) & 3)]);
+            if (rs < 0) {
+                fault = true;
+            } else {
+                const int r = rs >> 4, s = rs & 15;
+                if (s == 0) {
+                    k = r != 15 ? 64 : k + 16;
+                } else {
+                    k += r;
+                    if (k > 63) {
+                        fault = true;
+                    } else {
+                        br.fill();
+                        br.skip(s);
+                        k++;
+                    }
+                }
+            }
+            if (!fault && br.overrun()) return kStateEnd;
+        }
+        if (fault) {
+            if (br.overrun() || br.near_end()) return kStateEnd;
+            if (cc) cc->flags |= kChunkFault;
+            return kStateUnknown;
+        }
+        if (k >= 64) {
+            k = 0;
+            blk = blk + 1 == (int)sg.bpm ? 0 : blk + 1;
+        }
+    }
+    return kStateUnknown;      // never: max_steps covers the chunk's bits
+}
+
+// symbols a walk of one chunk can take: a symbol is at least one bit, and an entry lies less than 16 bytes past the start
+JPEG_HD inline uint32_t sync_max_steps(uint32_t chunk_bytes) { return chunk_bytes * 8u + 160u; }
+
+// the coefficient block of block j of a segment that starts at MCU mcu0 (decode_segment's arithmetic); false: outside the grid
+JPEG_HD inline bool seg_block_addr(const ImageDesc& im, uint32_t mcu0, uint32_t bpm, uint32_t j, uint32_t& blk, int& comp)
+{
+    const uint32_t m = mcu0 + j / bpm;
+    uint32_t i = j % bpm;
+    const uint32_t mx = m % (uint32_t)im.mcus_x, my = m / (uint32_t)im.mcus_x;
+    for (int c = 0; c < im.ncomp && c < 3; c++) {
+        const ScanComp sc = c == 0 ? im.comp[0] : c == 1 ? im.comp[1] : im.comp[2];
+        const uint32_t n = (uint32_t)(sc.h * sc.v);
+        if (i < n) {
+            const uint32_t row = my * (uint32_t)sc.v + i / (uint32_t)sc.h, col = mx * (uint32_t)sc.h + i % (uint32_t)sc.h;
+            if (row >= (uint32_t)sc.bh || col >= (uint32_t)sc.bw) return false;
+            blk = sc.coef_block + row * (uint32_t)sc.bw + col;
+            comp = c;
+            return true;
+        }
+        i -= n;
+    }
+    return false;
+}
+
+// Decodes the cc.nstart blocks that start in a chunk with decode_block, from the state cc.first,
+// block index j0 of the segment and the three predictors, into coef (the image's coefficient
+// area).  Blocks at or past sg.nblocks are not decoded.  Returns the fault bits (kStatus*).
+JPEG_HD inline int sync_write(const ImageDesc& im, const HuffTable* tables, const uint8_t* zz, const uint8_t* bytes,
+                              const SyncSeg& sg, const ChunkCount& cc, uint32_t j0, uint32_t p0, uint32_t p1, uint32_t p2,
+                              int16_t* coef)
+{
+    if (!cc.nstart || j0 >= sg.nblocks) return 0;
+    BitReader br;
+    br.init(bytes, (uint32_t)(cc.first >> 32), sg.end);
+    br.fill();
+    br.skip((int)(cc.first >> 16) & 7);
+    for (uint32_t i = 0, j = j0; i < cc.nstart && j < sg.nblocks; i++, j++) {
+        uint32_t blk = 0;
+        int c = 0;
+        if (!seg_block_addr(im, sg.mcu0, sg.bpm, j, blk, c)) return kStatusRun;      // never: the grid is built from the MCUs
+        const uint32_t info = (uint32_t)(sg.blkinfo >> (6 * (j % sg.bpm))) & 63u;
+        uint32_t pred = c == 0 ? p0 : c == 1 ? p1 : p2;
+        const int st = decode_block(br, tables[(info >> 2) & 3], tables[4 + ((info >> 4) & 3)], zz, pred, coef + (uint64_t)blk * 64u);
+        if (st) return st;
+        if (c == 0) p0 = pred;
+        else if (c == 1) p1 = pred;
+        else p2 = pred;
     }
     return 0;
 }

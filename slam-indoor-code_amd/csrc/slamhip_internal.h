@@ -319,6 +319,11 @@ struct slam_ctx {
     uint64_t jpeg_bytes[4] = {0, 0, 0, 0};
     bool jpeg_timed = false;
     int opt_jpeg_lanes = 0;               // SLAM_OPT_JPEG_LANES: 0 = by the segment count
+    // chunk-parallel entropy decoding (SLAM_OPT_JPEG_SYNC): segment table, chunk states, counts and statistics
+    int opt_jpeg_sync = 0, opt_jpeg_chunk = 0;
+    slamhip::DevBuf jpeg_sync;
+    hipEvent_t jpeg_sync_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    slam_jpeg_sync_stats jpeg_sync_stats = {};
     // scene rendering (render.hip): counters + per-view lists + the key buffer of one chunk of views;
     // slam_render's staged host primitives and its device result
     slamhip::DevBuf render_ws, render_in, render_out;

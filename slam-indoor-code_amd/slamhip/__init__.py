@@ -28,7 +28,9 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
                   buildOpticalFlowPyramid, calcOpticalFlowPyrLK, kltLevelSizes,
                   save_calibration, calibration_model,
                   imdecode, imread, imdecode_batch, jpegInfo, jpegLastTiming, applyOrientation,
+                  jpegLastSync, imdecode_host_sync, imdecode_host, jpegStdTable, aviIndex,
                   renderViews, renderCamera, renderStats)
+from .video import VideoCapture, write_mjpeg_avi
 from .config import ConfigError, ConfigService, reference_example
 from .calibration import CalibrationError, chessboard_photos_calibration
 

@@ -33,6 +33,9 @@ OPT_SIFT_BAND_SPLIT = 2
 OPT_PNP_SUMS = 3
 OPT_FAST_REUSE = 4
 OPT_JPEG_LANES = 5
+OPT_JPEG_SYNC = 6       # chunk-parallel entropy decoding: 0 off, 1 segments of at least 16 KiB, 2 every segment of more than a chunk
+OPT_JPEG_CHUNK = 7      # bytes per chunk: a power of two in 16 .. 1024, 0 = 256
+JPEG_MJPEG = 1          # parse flag of the _ex calls: a Motion-JPEG frame (Annex K tables when DHT is missing; AVI1 fields refused)
 PNP_SUMS_ORDERED, PNP_SUMS_PAIRWISE = 0, 1
 BAND_SPLIT_OFF, BAND_SPLIT_AUTO, BAND_SPLIT_ALL, BAND_SPLIT_ALL4 = 0, 1, 2, 3
 STAGE_DESC_START, STAGE_DESC_END = 0, 1     # slam_order_after_stage
@@ -67,6 +70,20 @@ class JpegInfo(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("channels", ctypes.c_int32),
                 ("sampling", ctypes.c_int32), ("restart_interval", ctypes.c_int32), ("segments", ctypes.c_int32),
                 ("orientation", ctypes.c_int32)]
+
+
+class JpegSyncStats(ctypes.Structure):
+    _fields_ = [("parallel_segments", ctypes.c_int32), ("fallback_segments", ctypes.c_int32),
+                ("chunk_bytes", ctypes.c_int32), ("lanes", ctypes.c_int32), ("chunks", ctypes.c_int64),
+                ("wg_rounds_max", ctypes.c_int32), ("launch_rounds_max", ctypes.c_int32),
+                ("wg_rounds_total", ctypes.c_int64), ("launch_rounds_total", ctypes.c_int64),
+                ("ms", ctypes.c_double * 5)]
+
+
+class AviInfo(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("rate", ctypes.c_uint32),
+                ("scale", ctypes.c_uint32), ("frames", ctypes.c_int64), ("handler", ctypes.c_uint32),
+                ("compression", ctypes.c_uint32), ("stream", ctypes.c_int32)]
 
 
 # exported symbols and their signatures: (restype, argtypes)
@@ -171,6 +188,14 @@ SIGNATURES = {
     "slam_jpeg_decode_batch_dev": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "slam_jpeg_last_orientations": (_I, [_P, _P, _I]),
     "slam_jpeg_last_timing": (_I, [_P, _P, _P]),
+    "slam_jpeg_info_ex": (_I, [_P, _SZ, _P, _I]),
+    "slam_jpeg_decode_host_ex": (_I, [_P, _SZ, _P, _SZ, _I, _I, _P]),
+    "slam_jpeg_decode_batch_dev_ex": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I]),
+    "slam_jpeg_std_table": (_I, [_I, _I, _P, _P, _P]),
+    "slam_jpeg_last_sync": (_I, [_P, _P]),
+    "slam_jpeg_decode_host_sync": (_I, [_P, _SZ, _P, _SZ, _I, _I, _I, _P, _P]),
+    "slam_avi_last_error": (ctypes.c_char_p, []),
+    "slam_avi_index": (_I, [_P, _SZ, _P, _P, _P, _SZ]),
     "slam_render_views_dev": (_I, [_P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _I]),
     "slam_render": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     "slam_render_last_stats": (_I, [_P, _P, _P]),

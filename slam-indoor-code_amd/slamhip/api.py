@@ -50,6 +50,11 @@ class Context:
         """slam_set_option: per-context choices (all but L.OPT_PNP_SUMS never change results; e.g.
         L.OPT_SIFT_KERNEL -> L.SIFT_KERNEL_BAND / _TAB / _GENERAL / _AUTO)."""
         L.check(lib().slam_set_option(self.handle, int(option), int(value)), self.handle)
+        self.__dict__.setdefault("_options", {})[int(option)] = int(value)
+
+    def get_option(self, option):
+        """the value last set through set_option (0, every option's default, when it never was)"""
+        return self.__dict__.get("_options", {}).get(int(option), 0)
 
     def close(self):
         self._det_out = None
@@ -1247,13 +1252,16 @@ def _jpeg_check(code, ctx=None):
         raise L.SlamError(code, msg.decode() if msg else "")
 
 
-def jpegInfo(buf):
-    """slam_jpeg_info: the stream's header as a dict (width, height, channels,
+def jpegInfo(buf, flags=0):
+    """slam_jpeg_info[_ex]: the stream's header as a dict (width, height, channels,
     sampling, restart_interval, segments, orientation); raises SlamError for a
-    stream the decoder does not take."""
+    stream the decoder does not take.  flags: L.JPEG_MJPEG."""
     a = _jpeg_bytes(buf)
     info = L.JpegInfo()
-    _jpeg_check(lib().slam_jpeg_info(ptr(a), a.size, ctypes.byref(info)))
+    if flags:
+        _jpeg_check(lib().slam_jpeg_info_ex(ptr(a), a.size, ctypes.byref(info), int(flags)))
+    else:
+        _jpeg_check(lib().slam_jpeg_info(ptr(a), a.size, ctypes.byref(info)))
     return {k: getattr(info, k) for k, _ in L.JpegInfo._fields_}
 
 
@@ -1313,12 +1321,15 @@ def imread(path, channels=3, apply_orientation=True, ctx=None, host=False):
         raise
 
 
-def imdecode_batch(bufs, ctx=None, out=None, size=None):
-    """slam_jpeg_decode_batch_dev: n JPEG streams of one size decoded into a
+def imdecode_batch(bufs, ctx=None, out=None, size=None, parallel=False, flags=0):
+    """slam_jpeg_decode_batch_dev[_ex]: n JPEG streams of one size decoded into a
     resident (n, h, w, 3) BGR torch tensor in one pass.  size: (w, h), by default
-    that of the first stream.  Returns (frames, status, orientations): status[i] is
-    0, the stream's entropy fault bits, or its negative SLAM_E_* (frame zeroed);
-    the orientations are not applied."""
+    that of the first stream.  parallel: SLAM_OPT_JPEG_SYNC is auto for this call
+    (large segments without restart markers are decoded by a lane per chunk; the
+    result is the same).  flags: L.JPEG_MJPEG for the frames of a Motion-JPEG
+    video.  Returns (frames, status, orientations): status[i] is 0, the stream's
+    entropy fault bits, or its negative SLAM_E_* (frame zeroed); the orientations
+    are not applied."""
     import torch
     ctx = ctx or default_context()
     arrs = [_jpeg_bytes(b) for b in bufs]
@@ -1326,7 +1337,7 @@ def imdecode_batch(bufs, ctx=None, out=None, size=None):
     if n == 0:
         raise ValueError("empty batch")
     if size is None:
-        first = jpegInfo(arrs[0])
+        first = jpegInfo(arrs[0], flags)
         size = (first["width"], first["height"])
     w, h = int(size[0]), int(size[1])
     if out is None:
@@ -1337,10 +1348,94 @@ def imdecode_batch(bufs, ctx=None, out=None, size=None):
     status = np.zeros(n, np.int32)
     orient = np.ones(n, np.int32)
     torch.cuda.current_stream(out.device).synchronize()
-    check(lib().slam_jpeg_decode_batch_dev(ctx.handle, None, ptrs, lens, n, w, h, ctypes.c_void_p(out.data_ptr()),
-                                           ptr(status)), ctx.handle)
+    sync_was = ctx.get_option(L.OPT_JPEG_SYNC)
+    if parallel and not sync_was:
+        ctx.set_option(L.OPT_JPEG_SYNC, 1)
+    try:
+        if flags:
+            check(lib().slam_jpeg_decode_batch_dev_ex(ctx.handle, None, ptrs, lens, n, w, h, ctypes.c_void_p(out.data_ptr()),
+                                                      ptr(status), int(flags)), ctx.handle)
+        else:
+            check(lib().slam_jpeg_decode_batch_dev(ctx.handle, None, ptrs, lens, n, w, h, ctypes.c_void_p(out.data_ptr()),
+                                                   ptr(status)), ctx.handle)
+    finally:
+        if parallel and not sync_was:
+            ctx.set_option(L.OPT_JPEG_SYNC, 0)
     check(lib().slam_jpeg_last_orientations(ctx.handle, ptr(orient), n), ctx.handle)
     return out, status, orient
+
+
+def _sync_stats(S):
+    d = {k: getattr(S, k) for k, _ in L.JpegSyncStats._fields_ if k != "ms"}
+    d["ms"] = dict(zip(("sync", "count", "scan", "write", "fallback"), list(S.ms)))
+    return d
+
+
+def jpegLastSync(ctx=None):
+    """slam_jpeg_last_sync: what the chunk-parallel path did in the context's last
+    batch decode, as a dict (parallel_segments, fallback_segments, chunk_bytes,
+    lanes, chunks, wg_rounds_max / _total, launch_rounds_max / _total, ms per kernel)."""
+    ctx = ctx or default_context()
+    S = L.JpegSyncStats()
+    check(lib().slam_jpeg_last_sync(ctx.handle, ctypes.byref(S)), ctx.handle)
+    return _sync_stats(S)
+
+
+def imdecode_host_sync(buf, chunk_bytes=0, flags=0, channels=3):
+    """slam_jpeg_decode_host_sync: the host decoder with every segment of more than
+    one chunk on the chunk-parallel path, in the kernels' round structure.  Returns
+    (frame, status, stats); the orientation is not applied."""
+    a = _jpeg_bytes(buf)
+    info = jpegInfo(a, flags)
+    out = np.empty((info["height"], info["width"], channels), np.uint8)
+    st = ctypes.c_int(0)
+    S = L.JpegSyncStats()
+    _jpeg_check(lib().slam_jpeg_decode_host_sync(ptr(a), a.size, ptr(out), out.strides[0], int(channels), int(chunk_bytes),
+                                                 int(flags), ctypes.byref(st), ctypes.byref(S)))
+    return out, st.value, _sync_stats(S)
+
+
+def imdecode_host(buf, flags=0, channels=3):
+    """slam_jpeg_decode_host_ex: (frame, status) of the serial host decoder under the parse flags"""
+    a = _jpeg_bytes(buf)
+    info = jpegInfo(a, flags)
+    out = np.empty((info["height"], info["width"], channels), np.uint8)
+    st = ctypes.c_int(0)
+    _jpeg_check(lib().slam_jpeg_decode_host_ex(ptr(a), a.size, ptr(out), out.strides[0], int(channels), int(flags),
+                                               ctypes.byref(st)))
+    return out, st.value
+
+
+def jpegStdTable(klass, slot):
+    """slam_jpeg_std_table: (counts[16], values) of the Annex K Huffman table of a class (0 DC, 1 AC) and slot (0, 1)"""
+    counts = np.zeros(16, np.uint8)
+    vals = np.zeros(256, np.uint8)
+    n = ctypes.c_int(0)
+    _jpeg_check(lib().slam_jpeg_std_table(int(klass), int(slot), ptr(counts), ptr(vals), ctypes.byref(n)))
+    return counts, vals[:n.value].copy()
+
+
+def aviIndex(buf):
+    """slam_avi_index over bytes (or an mmap / uint8 array) of an AVI file: (info
+    dict, offsets, sizes) of the frames of its Motion-JPEG video stream.  Raises
+    SlamError for what the walker refuses."""
+    a = np.frombuffer(buf, np.uint8) if not isinstance(buf, np.ndarray) else buf
+    info = L.AviInfo()
+
+    def call(off, siz, cap):
+        code = lib().slam_avi_index(ptr(a) if a.size else None, a.size, ctypes.byref(info), off, siz, cap)
+        if code != L.SLAM_OK:
+            msg = lib().slam_avi_last_error()
+            raise L.SlamError(code, msg.decode() if msg else "")
+    call(None, None, 0)
+    n = int(info.frames)
+    offsets = np.zeros(n, np.uint64)
+    sizes = np.zeros(n, np.uint64)
+    if n:
+        call(ptr(offsets), ptr(sizes), n)
+    d = {k: getattr(info, k) for k, _ in L.AviInfo._fields_}
+    d["fps"] = info.rate / info.scale if info.scale else 0.0
+    return d, offsets, sizes
 
 
 def jpegLastTiming(ctx=None):

@@ -642,9 +642,10 @@ class JpegMedia:
     a stream the decoder refuses raises SlamError, entropy faults (status bits) are
     kept in `faults` and the frame is used as decoded."""
 
-    def __init__(self, paths_or_buffers, ops, chunk=32):
+    def __init__(self, paths_or_buffers, ops, chunk=32, parallel=False):
         self._items = list(paths_or_buffers)
         self.ops, self.chunk = ops, max(1, int(chunk))
+        self.parallel = bool(parallel)      # SLAM_OPT_JPEG_SYNC auto: a lane per chunk for photos without restart markers
         self._pos = 0            # the next item to decode
         self._seq = None         # DeviceMedia over the current chunk
         self._size = None
@@ -660,7 +661,7 @@ class JpegMedia:
                 with open(it, "rb") as f:
                     it = f.read()
             bufs.append(it)
-        dev, status, orient = api.imdecode_batch(bufs, ctx=self.ops.ctx, size=self._size)
+        dev, status, orient = api.imdecode_batch(bufs, ctx=self.ops.ctx, size=self._size, parallel=self.parallel)
         for k, st in enumerate(status):
             if st < 0:
                 raise L.SlamError(int(st), f"JPEG stream {self._pos + k} cannot be decoded")
@@ -696,6 +697,56 @@ class JpegMedia:
     def next_frame(self):
         f = self.take(1)
         return f[0] if f else None
+
+
+class VideoMedia:
+    """MediaSources over a Motion-JPEG AVI file (the reference's videoSourcePath
+    input, VideoCapture::read of every frame) decoded on the device: take(n)
+    decodes the next max(n, chunk) frames in one VideoCapture.read_batch straight
+    from the mapped file and hands out ResidentFrames that are views of one
+    contiguous resident range, as JpegMedia does; the host copy is fetched once
+    per chunk.  A frame the decoder refuses raises SlamError; entropy faults are
+    kept in `faults` and the frame is used as decoded."""
+
+    def __init__(self, path, ops, chunk=32):
+        from . import video
+        self.ops, self.chunk = ops, max(1, int(chunk))
+        self.cap = video.VideoCapture(path, ctx=ops.ctx)
+        if not self.cap.isOpened():
+            raise self.cap.error if self.cap.error is not None else OSError(f"cannot open {path}")
+        self._seq = None
+        self.faults = {}
+
+    def _decode(self, n):
+        first = int(self.cap.get(1))
+        dev, status = self.cap.read_batch(n)
+        for k, st in enumerate(status):
+            if st < 0:
+                raise L.SlamError(int(st), f"video frame {first + k} cannot be decoded")
+            if st:
+                self.faults[first + k] = int(st)
+        self._seq = DeviceMedia(dev.cpu().numpy(), dev)
+
+    def take(self, n):
+        if self._seq is None or self._seq.i >= len(self._seq.dev):
+            left = int(self.cap.get(7)) - int(self.cap.get(1))
+            if left <= 0 or n <= 0:
+                return []
+            self._decode(min(left, max(n, self.chunk)))
+        return self._seq.take(n)
+
+    def next_frame(self):
+        f = self.take(1)
+        return f[0] if f else None
+
+
+def media_from_config(cfg, ops, chunk=32):
+    """defineMediaSources: usePhotosCycle -> JpegMedia over the sorted paths that
+    photosPathPattern matches (cv::glob sorts), else VideoMedia over videoSourcePath."""
+    import glob
+    if cfg.getValue("usePhotosCycle"):
+        return JpegMedia(sorted(glob.glob(cfg.getValue("photosPathPattern"))), ops, chunk=chunk)
+    return VideoMedia(cfg.getValue("videoSourcePath"), ops, chunk=chunk)
 
 
 def _is_fisheye(lens_model):
@@ -750,7 +801,7 @@ class UndistortedMedia:
 class MediaSources:
     """MediaSources + getNextFrame (mainCycleInternals.cpp:107-120) over an
     in-memory sequence, a list of image paths (decoded with PIL, as imread
-    would give BGR) or .npy frames.  Video decoding is out of scope."""
+    would give BGR) or .npy frames.  Motion-JPEG video: VideoMedia."""
 
     def __init__(self, frames=None, paths=None):
         self._frames = list(frames) if frames is not None else []
