@@ -145,7 +145,8 @@ int slam_describe(slam_ctx* ctx, const uint8_t* img, int w, int h, size_t step, 
  * image).  Keypoints come in OpenCV's order (KeyPointsFilter::
  * removeDuplicatedSorted), octave packed as OpenCV packs it.  *n_out = total
  * found; SLAM_E_CAPACITY if > cap (the first cap are written).  desc
- * (nullable): cap x 128 float, integer values 0..255. */
+ * (nullable): cap x 128 float, integer values 0..255.  A frame 1 pixel wide or
+ * tall has no octave (as in OpenCV): SLAM_OK and no keypoints. */
 int slam_sift_detect(slam_ctx* ctx, const uint8_t* img, int w, int h, size_t step, int channels,
                      slam_keypoint* kps, int cap, int* n_out, float* desc);
 
@@ -1012,6 +1013,21 @@ enum slam_knn_variant { SLAM_KNN_VARIANT_NONE = 0, SLAM_KNN_VARIANT_MFMA = 1, SL
                         SLAM_KNN_VARIANT_MFMA_PK_QT1 = 3, SLAM_KNN_VARIANT_PIPE_QT2 = 4,
                         SLAM_KNN_VARIANT_PIPE_QT1 = 5, SLAM_KNN_VARIANT_L1 = 6, SLAM_KNN_VARIANT_XCD = 0x100 };
 int slam_last_knn_launch(const slam_ctx* ctx, int* mode, int* tsplit, int* variant);
+
+/* which forms of the full SIFT detector the context's last slam_sift_detect /
+ * slam_sift_detect_batch call ran (the last one that launched anything: a call
+ * that returns before its first launch leaves them as they were).  *forms: the
+ * SLAM_SD_FORM_* bits -- DoG planes stored by the blurs (else taken from the
+ * Gaussian layers), pyramid and extrema tiles in XCD-contiguous order, and, set
+ * by the call's descriptor launch only (no bits without one): the staged
+ * descriptor kernel (else the direct one), two cells per lane, its blocks in
+ * XCD-contiguous order.  *refine_blocks: sd_refine's grid size.  Either pointer
+ * may be NULL.  Returns SLAM_OK, or SLAM_E_INVALID_ARG before the context's first
+ * such call.  For tests: the forms are chosen once per process and never
+ * change results. */
+enum slam_sd_form { SLAM_SD_FORM_DOG_PLANES = 1, SLAM_SD_FORM_XCD = 2, SLAM_SD_FORM_DESC_STAGED = 4,
+                    SLAM_SD_FORM_DESC_CPL2 = 8, SLAM_SD_FORM_DESC_XCD = 16 };
+int slam_last_sift_detect_forms(const slam_ctx* ctx, int* forms, int* refine_blocks);
 
 /* ---- profiling hooks (bench.py) ---------------------------------------------- */
 /* average duration (ms) of the last batch's launches of one kernel family,

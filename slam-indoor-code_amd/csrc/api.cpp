@@ -1995,6 +1995,14 @@ int slam_last_knn_launch(const slam_ctx* c, int* mode, int* tsplit, int* variant
     return SLAM_OK;
 }
 
+int slam_last_sift_detect_forms(const slam_ctx* c, int* forms, int* refine_blocks)
+{
+    if (!c || c->last_sd_forms < 0) return SLAM_E_INVALID_ARG;
+    if (forms) *forms = c->last_sd_forms;
+    if (refine_blocks) *refine_blocks = c->last_sd_refine_blocks;
+    return SLAM_OK;
+}
+
 int slam_batch_get_matches(slam_ctx* c, int frame, slam_dmatch* out, int cap, int* n)
 {
     if (!c || !n || frame < 0 || frame >= c->batch.nframes || !c->batch.have_matches) return SLAM_E_INVALID_ARG;

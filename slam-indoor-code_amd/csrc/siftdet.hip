@@ -1515,10 +1515,21 @@ static int sd_refine_blocks()
 static int sift_detect_frames(slam_ctx* c, hipStream_t s, int nf, int w, int h, slam_keypoint* out, int cap,
                               int* n_out, float* desc, bool dev_out)
 {
+    if (nf <= 0 || nf > kSiftDetectMaxFrames) return set_err(c, SLAM_E_INVALID_ARG, "detector batch size");
     const bool dogless = !sd_dog_planes();
     PyrInfo P;
     size_t total;
     pyr_layout(w, h, P, total, !dogless);
+    if (P.n <= 0) {
+        // a frame 1 pixel wide or tall: cvRound(log2(2) - 2) + 1 = 0 octaves, an
+        // empty pyramid and no keypoints (nothing to launch into)
+        for (int f = 0; f < nf; f++) n_out[f] = 0;
+        return SLAM_OK;
+    }
+    // the forms this call runs (slam_last_sift_detect_forms); the descriptor
+    // launch adds its own below
+    c->last_sd_forms = (dogless ? 0 : SLAM_SD_FORM_DOG_PLANES) | (sd_xcd_on() ? SLAM_SD_FORM_XCD : 0);
+    c->last_sd_refine_blocks = sd_refine_blocks();
     const size_t fT = total, fD = (size_t)4 * w * h;          // pyramid / doubled-base floats per frame
     SLAM_HIP(c, c->sd_pyr.ensure((size_t)nf * fT * sizeof(float)));
     float* pyr = c->sd_pyr.as<float>();
@@ -1580,7 +1591,6 @@ static int sift_detect_frames(slam_ctx* c, hipStream_t s, int nf, int w, int h, 
             SLAM_HIP(c, blur(pyr + O.g[i - 1], fT, pyr + O.g[i], dogless ? nullptr : pyr + O.d[i - 1], O.w, O.h, sig[i]));
     }
     // extrema candidates ({octave | frame << 8, layer, r, c}) of every frame
-    if (nf <= 0 || nf > kSiftDetectMaxFrames) return set_err(c, SLAM_E_INVALID_ARG, "detector batch size");
     const int ccap = nf << 20, kcap_f = 1 << 20, kcap = nf * kcap_f;   // <= 2^28: int-indexed in the kernels
     SLAM_HIP(c, c->sd_cand.ensure((size_t)ccap * sizeof(int4)));
     SLAM_HIP(c, c->sd_kps.ensure((size_t)kcap * sizeof(slam_keypoint)));
@@ -1762,6 +1772,8 @@ static int sift_detect_frames(slam_ctx* c, hipStream_t s, int nf, int w, int h, 
         // 1215 / 1219 frames/s, bit-exact); SLAMHIP_SD_DESC_XCD=0: the plain order
         static const int dxcd = [] { const char* e = getenv("SLAMHIP_SD_DESC_XCD"); return e && e[0] == '0' ? 0 : 1; }();
         dp.xcd = dxcd;
+        c->last_sd_forms |= (form != 0 ? SLAM_SD_FORM_DESC_STAGED : 0) | (form != 0 && cpl != 1 ? SLAM_SD_FORM_DESC_CPL2 : 0) |
+                            (form != 0 && dxcd ? SLAM_SD_FORM_DESC_XCD : 0);   // the direct kernel has no XCD order
         const int kpb = cpl == 1 ? 16 : 32;      // keypoints per block
         const dim3 dgrid(std::min((nd + kpb - 1) / kpb, 8192));
         if (form == 0)

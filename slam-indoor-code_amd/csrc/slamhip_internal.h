@@ -356,6 +356,8 @@ struct slam_ctx {
     int last_sift_kernel = 0;             // SLAM_SIFT_KERNEL_* of the last descriptor launch
     // the last launch_knn: key mode, split count, SLAM_KNN_VARIANT_* (slam_last_knn_launch)
     int last_knn_mode = -1, last_knn_tsplit = 0, last_knn_variant = 0;
+    // the last SIFT detector call that launched: SLAM_SD_FORM_* and sd_refine's grid (slam_last_sift_detect_forms)
+    int last_sd_forms = -1, last_sd_refine_blocks = 0;
     hipEvent_t ev_order = nullptr;        // slam_order_after
     hipEvent_t ev_stage[2] = {nullptr, nullptr};   // the last extraction's descriptor start / end
     bool stage_recorded = false;

@@ -16,7 +16,7 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
                   bundleAdjustment, default_context, extractDescriptor, fastExtractor, getGoodMatches,
                   estimateTransformation, reconstruct, siftDetectAndCompute, siftDetectAndComputeBatch, SiftBatch, solvePnPRansac,
                   orbDetectAndCompute, orbDetectAndComputeBatch, OrbBatch,
-                  getMatcherTypeIndex, knnMatch2, lastKnnLaunch, loss_from_config, matchFeatures, matchFramesPairFeatures,
+                  getMatcherTypeIndex, knnMatch2, lastKnnLaunch, lastSiftDetectForms, loss_from_config, matchFeatures, matchFramesPairFeatures,
                   rodrigues_to_matrix, rodrigues_to_vector, selectGoodFrame, synth_frames,
                   SYNTH_DRIFT, SYNTH_STEADY, synth_frames_dev,
                   clusterizePoints, clusterLabels, getBestFittingPlaneByPoints, planeMoments, projectToPlane,

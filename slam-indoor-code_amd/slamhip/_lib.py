@@ -43,6 +43,7 @@ KNN_MODE_L2, KNN_MODE_SQRT, KNN_MODE_L2_PACKED, KNN_MODE_HAMMING_PACKED, KNN_MOD
 (KNN_VARIANT_MFMA, KNN_VARIANT_MFMA_PK_QT2, KNN_VARIANT_MFMA_PK_QT1, KNN_VARIANT_PIPE_QT2, KNN_VARIANT_PIPE_QT1,
  KNN_VARIANT_L1) = range(1, 7)
 KNN_VARIANT_XCD = 0x100
+SD_FORM_DOG_PLANES, SD_FORM_XCD, SD_FORM_DESC_STAGED, SD_FORM_DESC_CPL2, SD_FORM_DESC_XCD = 1, 2, 4, 8, 16   # slam_last_sift_detect_forms
 KLT_USE_INITIAL_FLOW, KLT_GET_MIN_EIGENVALS = 4, 8     # cv::OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS
 KLT_MAX_LEVELS = 9                                     # maxLevel 0..8
 JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = 0, 0x11, 0x21, 0x22      # slam_jpeg_info's sampling
@@ -138,6 +139,7 @@ SIGNATURES = {
     "slam_batch_fast_reused": (_I, [_P]),
     "slam_last_sift_kernel": (_I, [_P]),
     "slam_last_knn_launch": (_I, [_P, _P, _P, _P]),
+    "slam_last_sift_detect_forms": (_I, [_P, _P, _P]),
     "slam_profile_enable": (_I, [_P, _I]),
     "slam_profile_read": (_I, [_P, _I, _P, _P]),
     "slam_synth_frames": (_I, [_I, _I, _I, _I, _U64, _P]),

@@ -378,6 +378,15 @@ def lastKnnLaunch(ctx=None):
     return mode.value, tsplit.value, variant.value
 
 
+def lastSiftDetectForms(ctx=None):
+    """(forms, refine_blocks) of the context's last SIFT detector call
+    (slam_last_sift_detect_forms): L.SD_FORM_* bits and sd_refine's grid size."""
+    c = _ctx(ctx)
+    forms, blocks = ctypes.c_int(-1), ctypes.c_int(0)
+    check(lib().slam_last_sift_detect_forms(c, ctypes.byref(forms), ctypes.byref(blocks)), c)
+    return forms.value, blocks.value
+
+
 def getGoodMatches(idx, dist, knnMatcherDistance):
     """featureMatchingCommon.cpp:37-50 on knnMatch2 output (query order)."""
     ok = (idx[:, 0] >= 0) & (idx[:, 1] >= 0)
