@@ -903,6 +903,58 @@ const char* slam_avi_last_error(void);
 int slam_avi_index(const uint8_t* buf, size_t len, struct slam_avi_info* info, uint64_t* offsets, uint64_t* sizes,
                    size_t cap);
 
+/* ---- JPEG encoding: cv::imencode / cv::imwrite of baseline JPEG ------------------ */
+/* What cv::imencode(".jpg") and PIL's save(format="JPEG") run: libjpeg's encoder
+ * with its defaults (jpeg_set_defaults, jpeg_set_quality(q, TRUE), JDCT_ISLOW, the
+ * Annex K Huffman tables, no optimisation, no smoothing), restated in 32-bit
+ * integers; the numpy restatement tests/jpeg_enc_ref.py is the contract, and the
+ * host encoder and the kernels equal it byte for byte.
+ * Frames: 8-bit, 3 channels (BGR) or 1 (gray; written as a gray stream whatever the
+ * sampling), 1 .. 16384 pixels a side.  sampling: SLAM_JPEG_444, _422, _420, or
+ * SLAM_JPEG_GRAY (a BGR frame's luma alone).  quality is clamped to 1 .. 100.
+ * restart_interval: MCUs per restart interval, 0 .. 65535, 0 = none.
+ * Not written: optimised tables, progressive / arithmetic / 12-bit streams, 4:4:0
+ * and 4:1:1, Exif.
+ * The stream length is known before a byte is written: size always reports the
+ * length needed.  When it exceeds the capacity, the first cap bytes are written,
+ * nothing at or past the capacity, status carries SLAM_JPEG_ENC_OVERFLOW and the
+ * call still returns SLAM_OK.  SLAM_JPEG_ENC_CATEGORY: a coefficient past the
+ * Huffman tables' categories (11 for DC, 10 for AC), which 8-bit input cannot
+ * produce; it is clamped, and no table is indexed past its end. */
+enum slam_jpeg_enc_status { SLAM_JPEG_ENC_OVERFLOW = 1, SLAM_JPEG_ENC_CATEGORY = 2 };
+/* A capacity no stream of this geometry exceeds (0 for arguments slam_jpeg_encode
+ * refuses).  Derivation: a block is at most an 11-bit DC code with 11 more bits and
+ * 63 AC terms of a 16-bit code with 10 more bits, 1660 bits; every restart interval
+ * adds at most one byte of padding; every scan byte may be FF and so doubles;
+ * every interval but the last is followed by a 2-byte RSTn; the markers SOI .. SOS
+ * are 629 bytes at the most (640 is taken); EOI is 2:
+ *   640 + 2 (ceil(1660 blocks / 8) + intervals) + 2 intervals + 2. */
+size_t slam_jpeg_encode_bound(int h, int w, int sampling, int restart_interval);
+/* the whole encoder on the host (the contract of slam_jpeg_encode) */
+int slam_jpeg_encode_host(const uint8_t* img, int h, int w, int channels, size_t row_step, int quality, int sampling,
+                          int restart_interval, uint8_t* out, size_t cap, size_t* size, int* status);
+/* the message of the calling thread's last failing slam_jpeg_encode_host / slam_jpeg_encode_bound */
+const char* slam_jpeg_enc_last_error(void);
+/* one host image through the device encoder (status nullable) */
+int slam_jpeg_encode(slam_ctx* ctx, const uint8_t* img, int h, int w, int channels, size_t row_step, int quality,
+                     int sampling, int restart_interval, uint8_t* out, size_t cap, size_t* size, int* status);
+/* n resident frames of one size (frame i at frames_dev + i frame_step, rows
+ * row_step apart) into n streams, one set of launches for the batch: stream i goes
+ * to out_dev + i cap_per_image, its length to sizes_dev[i], its status bits to
+ * status_dev[i] (all device memory).  n: 1 .. 65535 (an image is a row of the
+ * launch grid), else SLAM_E_INVALID_ARG.  stream: a hipStream_t, NULL = the context's.
+ * Synchronous: the unstuffed lengths are read back once mid-way to size the
+ * stuffing pass. */
+int slam_jpeg_encode_batch_dev(slam_ctx* ctx, void* stream, const uint8_t* frames_dev, int n, int h, int w, int channels,
+                               size_t row_step, size_t frame_step, int quality, int sampling, int restart_interval,
+                               uint8_t* out_dev, size_t cap_per_image, uint64_t* sizes_dev, int32_t* status_dev);
+/* timing of the context's last device encode, in ms: 0 jpeg_enc_dct, 1
+ * jpeg_enc_count, 2 the tile scans with jpeg_enc_intervals, 3 the readback of the
+ * lengths, 4 clearing + jpeg_enc_pack, 5 jpeg_enc_ffcount + its scan, 6
+ * jpeg_enc_write; bytes (may be NULL): 0 frames read, 1 coefficients (written
+ * once, read twice), 2 unstuffed streams, 3 read back mid-way */
+int slam_jpeg_enc_last_timing(slam_ctx* ctx, double* ms7, uint64_t* bytes4);
+
 /* ---- scene rendering (the cv::viz window of vizualizePointsAndCameras, headless) -- */
 /* A deterministic z-buffer rasteriser for the onlyViz scene: the coloured cloud
  * (WCloud: n_pts x 3 f32 points, n_pts x 3 u8 BGR colours), the meshes (WMesh:

@@ -424,6 +424,7 @@ void slam_destroy(slam_ctx* c)
                       &c->calib_resp, &c->calib_mask, &c->calib_out, &c->calib_sub,
                       &c->klt_img, &c->klt_pyr, &c->klt_deriv, &c->klt_pts,
                       &c->jpeg_in, &c->jpeg_coef, &c->jpeg_planes, &c->jpeg_out, &c->jpeg_sync,
+                      &c->jenc_ws, &c->jenc_coef, &c->jenc_bits, &c->jenc_ff, &c->jenc_io,
                       &c->render_ws, &c->render_in, &c->render_out};
     for (DevBuf* b : bufs) b->release();
     if (c->h_up) (void)hipHostFree(c->h_up);
@@ -437,6 +438,7 @@ void slam_destroy(slam_ctx* c)
         if (e) (void)hipEventDestroy(e);
     if (c->h_async) (void)hipHostFree(c->h_async);
     jpeg_release(c);
+    jpeg_enc_release(c);
     render_release(c);
     for (auto& f : c->prof)
         for (hipEvent_t e : f.ev) (void)hipEventDestroy(e);

@@ -324,6 +324,13 @@ struct slam_ctx {
     slamhip::DevBuf jpeg_sync;
     hipEvent_t jpeg_sync_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     slam_jpeg_sync_stats jpeg_sync_stats = {};
+    // JPEG encoding (jpeg_enc.hip): parameters + scans, coefficients, the unstuffed streams, the FF counts,
+    // and slam_jpeg_encode's device frame, stream, size and status
+    slamhip::DevBuf jenc_ws, jenc_coef, jenc_bits, jenc_ff, jenc_io;
+    hipEvent_t jenc_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    double jenc_ms[7] = {0, 0, 0, 0, 0, 0, 0};      // slam_jpeg_enc_last_timing
+    uint64_t jenc_bytes[4] = {0, 0, 0, 0};
+    bool jenc_timed = false;
     // scene rendering (render.hip): counters + per-view lists + the key buffer of one chunk of views;
     // slam_render's staged host primitives and its device result
     slamhip::DevBuf render_ws, render_in, render_out;
@@ -650,6 +657,8 @@ hipError_t launch_klt_track(hipStream_t s, const KltLayout& L, const uint8_t* pr
 // ---- JPEG decoding (jpeg.hip) ----
 // frees the context's host-side JPEG state (pinned staging, parsed headers, events)
 void jpeg_release(slam_ctx* c);
+// ---- JPEG encoding (jpeg_enc.hip) ----
+void jpeg_enc_release(slam_ctx* c);
 
 // ---- scene rendering (render.hip) ----
 // destroys the context's render events

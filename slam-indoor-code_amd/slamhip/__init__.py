@@ -29,8 +29,11 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
                   save_calibration, calibration_model,
                   imdecode, imread, imdecode_batch, jpegInfo, jpegLastTiming, applyOrientation,
                   jpegLastSync, imdecode_host_sync, imdecode_host, jpegStdTable, aviIndex,
+                  imencode, imwrite, imencode_batch, jpegEncode, jpegEncodeBound, jpegEncLastTiming,
+                  IMWRITE_JPEG_QUALITY, IMWRITE_JPEG_RST_INTERVAL, IMWRITE_JPEG_SAMPLING_FACTOR,
+                  IMWRITE_JPEG_SAMPLING_FACTOR_420, IMWRITE_JPEG_SAMPLING_FACTOR_422, IMWRITE_JPEG_SAMPLING_FACTOR_444,
                   renderViews, renderCamera, renderStats)
-from .video import VideoCapture, write_mjpeg_avi
+from .video import VideoCapture, VideoWriter, write_mjpeg_avi
 from .config import ConfigError, ConfigService, reference_example
 from .calibration import CalibrationError, chessboard_photos_calibration
 

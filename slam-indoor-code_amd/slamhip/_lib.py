@@ -48,6 +48,7 @@ KLT_USE_INITIAL_FLOW, KLT_GET_MIN_EIGENVALS = 4, 8     # cv::OPTFLOW_USE_INITIAL
 KLT_MAX_LEVELS = 9                                     # maxLevel 0..8
 JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = 0, 0x11, 0x21, 0x22      # slam_jpeg_info's sampling
 JPEG_EOF, JPEG_BAD_CODE, JPEG_RUN, JPEG_RESTART = 1, 2, 4, 8       # entropy fault bits of a decode's status
+JPEG_ENC_OVERFLOW, JPEG_ENC_CATEGORY = 1, 2                        # status bits of an encode
 RENDER_POINT, RENDER_LINE, RENDER_FACE = 0, 1, 2                   # the kind in a rendered id (kind << 30 | index)
 RENDER_AUTO, RENDER_THREAD, RENDER_WAVE, RENDER_WAVE_FULL_LIST = 0, 1, 2, 3   # slam_render_views_dev's raster_mode
 SIFT_KERNEL_AUTO, SIFT_KERNEL_BAND,SIFT_KERNEL_TAB, SIFT_KERNEL_GENERAL, SIFT_KERNEL_COLS, SIFT_KERNEL_COLW = 0, 1, 2, 3, 4, 5
@@ -198,6 +199,12 @@ SIGNATURES = {
     "slam_jpeg_decode_host_sync": (_I, [_P, _SZ, _P, _SZ, _I, _I, _I, _P, _P]),
     "slam_avi_last_error": (ctypes.c_char_p, []),
     "slam_avi_index": (_I, [_P, _SZ, _P, _P, _P, _SZ]),
+    "slam_jpeg_encode_bound": (_SZ, [_I, _I, _I, _I]),
+    "slam_jpeg_encode_host": (_I, [_P, _I, _I, _I, _SZ, _I, _I, _I, _P, _SZ, _P, _P]),
+    "slam_jpeg_enc_last_error": (ctypes.c_char_p, []),
+    "slam_jpeg_encode": (_I, [_P, _P, _I, _I, _I, _SZ, _I, _I, _I, _P, _SZ, _P, _P]),
+    "slam_jpeg_encode_batch_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, _SZ, _SZ, _I, _I, _I, _P, _SZ, _P, _P]),
+    "slam_jpeg_enc_last_timing": (_I, [_P, _P, _P]),
     "slam_render_views_dev": (_I, [_P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _I]),
     "slam_render": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     "slam_render_last_stats": (_I, [_P, _P, _P]),

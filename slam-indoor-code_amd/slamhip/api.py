@@ -18,6 +18,7 @@ Every computation runs in the HIP library on the GPU; there is no CPU path.
 """
 import ctypes
 import math
+import os
 
 import numpy as np
 
@@ -1562,3 +1563,158 @@ def renderStats(ctx=None):
     check(lib().slam_render_last_stats(ctx.handle, ptr(st), ptr(ms)), ctx.handle)
     return (dict(zip(("primitives", "skipped", "clipped", "rasterised", "fragments"), [int(v) for v in st])),
             dict(zip(("clear_ms", "points_lines_ms", "faces_ms", "resolve_ms"), ms.tolist())))
+
+
+# ---- JPEG encoding: cv::imencode / cv::imwrite on baseline JPEG (jpeg_enc.hip, jpeg_enc_host.cpp) ----
+# cv::ImwriteFlags and cv::ImwriteJPEGSamplingFactorParams, quoted from memory of OpenCV 4.8's
+# imgcodecs.hpp (the headers are not part of this repository)
+IMWRITE_JPEG_QUALITY = 1
+IMWRITE_JPEG_RST_INTERVAL = 4
+IMWRITE_JPEG_SAMPLING_FACTOR = 7
+IMWRITE_JPEG_SAMPLING_FACTOR_420 = 0x221111
+IMWRITE_JPEG_SAMPLING_FACTOR_422 = 0x211111
+IMWRITE_JPEG_SAMPLING_FACTOR_444 = 0x111111
+_JPEG_SAMPLING = {IMWRITE_JPEG_SAMPLING_FACTOR_420: L.JPEG_420, IMWRITE_JPEG_SAMPLING_FACTOR_422: L.JPEG_422,
+                  IMWRITE_JPEG_SAMPLING_FACTOR_444: L.JPEG_444}
+JPEG_ENC_HEADER_ROOM = 1024      # imencode_batch's first capacity: the pixels' bytes and this
+
+
+def _jpeg_params(params):
+    p = [int(v) for v in params]
+    if len(p) & 1:
+        raise ValueError("params: (flag, value) pairs")
+    quality, restart, sampling = 95, 0, L.JPEG_420
+    for k, v in zip(p[0::2], p[1::2]):
+        if k == IMWRITE_JPEG_QUALITY:
+            quality = min(max(v, 0), 100)
+        elif k == IMWRITE_JPEG_RST_INTERVAL:
+            restart = min(max(v, 0), 65535)
+        elif k == IMWRITE_JPEG_SAMPLING_FACTOR:
+            if v not in _JPEG_SAMPLING:
+                raise L.SlamError(L.SLAM_E_UNSUPPORTED, f"sampling factor {v:#x}: 4:2:0, 4:2:2 and 4:4:4 are written")
+            sampling = _JPEG_SAMPLING[v]
+    return quality, sampling, restart
+
+
+def _enc_image(img):
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3)) or a.size == 0:
+        raise TypeError("an image to encode is a non-empty (h, w), (h, w, 1) or (h, w, 3) uint8 array")
+    return np.ascontiguousarray(a)
+
+
+def jpegEncodeBound(h, w, sampling=L.JPEG_420, restart_interval=0):
+    """slam_jpeg_encode_bound: a capacity that no stream of this geometry exceeds"""
+    return int(lib().slam_jpeg_encode_bound(int(h), int(w), int(sampling), int(restart_interval)))
+
+
+def jpegEncode(img, quality=95, sampling=L.JPEG_420, restart_interval=0, ctx=None, host=False, cap=None):
+    """slam_jpeg_encode (device) or slam_jpeg_encode_host of one (h, w[, 3]) uint8
+    image (BGR or gray).  cap: the capacity offered (default: the bound).  Returns
+    (bytes written, size needed, status bits)."""
+    a = _enc_image(img)
+    h, w = a.shape[:2]
+    ch = 1 if a.ndim == 2 else a.shape[2]
+    if cap is None:
+        cap = jpegEncodeBound(h, w, sampling, restart_interval)
+    out = np.empty(max(int(cap), 1), np.uint8)
+    size = ctypes.c_size_t(0)
+    st = ctypes.c_int(0)
+    if host:
+        code = lib().slam_jpeg_encode_host(ptr(a), h, w, ch, a.strides[0], int(quality), int(sampling), int(restart_interval),
+                                           ptr(out), int(cap), ctypes.byref(size), ctypes.byref(st))
+        if code != L.SLAM_OK:
+            msg = lib().slam_jpeg_enc_last_error()
+            raise L.SlamError(code, msg.decode() if msg else "")
+    else:
+        ctx = ctx or default_context()
+        check(lib().slam_jpeg_encode(ctx.handle, ptr(a), h, w, ch, a.strides[0], int(quality), int(sampling),
+                                     int(restart_interval), ptr(out), int(cap), ctypes.byref(size), ctypes.byref(st)),
+              ctx.handle)
+    return out[:min(size.value, int(cap))].tobytes(), size.value, st.value
+
+
+def imencode(ext, img, params=(), ctx=None, host=False):
+    """cv::imencode(ext, img, params) for ".jpg" / ".jpeg": (ok, bytes), encoded on
+    the device (host=True: the same arithmetic on the host, no GPU needed).  img:
+    (h, w, 3) BGR or (h, w) gray uint8.  params: IMWRITE_JPEG_QUALITY (default 95),
+    IMWRITE_JPEG_RST_INTERVAL (MCUs, default 0) and IMWRITE_JPEG_SAMPLING_FACTOR
+    (default 4:2:0, libjpeg's).  The flags' numeric values and the 4:2:0 default are
+    quoted from memory of OpenCV 4.8 (imgcodecs.hpp, grfmt_jpeg.cpp), not read from
+    its sources.  The bytes are libjpeg's with its defaults (tests/jpeg_enc_ref.py);
+    another extension gives (False, b"")."""
+    if str(ext).lower() not in (".jpg", ".jpeg"):
+        return False, b""
+    quality, sampling, restart = _jpeg_params(params)
+    data, size, st = jpegEncode(img, quality, sampling, restart, ctx=ctx, host=host)
+    return (st == 0 and size == len(data)), data
+
+
+def imwrite(path, img, params=(), ctx=None, host=False):
+    """cv::imwrite(path, img, params) for a .jpg / .jpeg name: imencode's bytes in a file; False when
+    the extension is another or the file cannot be written."""
+    ok, data = imencode(os.path.splitext(str(path))[1], img, params, ctx=ctx, host=host)
+    if not ok:
+        return False
+    try:
+        with open(path, "wb") as f:
+            f.write(data)
+    except OSError:
+        return False
+    return True
+
+
+def imencode_batch(frames, quality=95, sampling=L.JPEG_420, restart_interval=0, ctx=None):
+    """slam_jpeg_encode_batch_dev: n frames of one size, a resident (n, h, w, 3) /
+    (n, h, w) uint8 torch tensor or a numpy array (uploaded), encoded in one set of
+    launches.  Returns a list of n bytes objects.  The first call offers h w channels
+    + JPEG_ENC_HEADER_ROOM bytes per image; images that overflow it are encoded once
+    more with the largest size reported."""
+    import torch
+    ctx = ctx or default_context()
+    dev = torch.device("cuda", ctx.device)
+    if not isinstance(frames, torch.Tensor):
+        frames = torch.from_numpy(np.ascontiguousarray(frames)).to(dev)
+    if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or frames.numel() == 0 or \
+            (frames.dim() == 4 and frames.shape[3] not in (1, 3)):
+        raise TypeError("frames: a non-empty (n, h, w, 3) or (n, h, w) uint8 batch")
+    frames = frames.contiguous()
+    n, h, w = (int(v) for v in frames.shape[:3])
+    ch = 1 if frames.dim() == 3 else int(frames.shape[3])
+
+    def run(fr, cap):
+        k = int(fr.shape[0])
+        out = torch.empty((k, cap), dtype=torch.uint8, device=dev)
+        sizes = torch.zeros(k, dtype=torch.int64, device=dev)
+        status = torch.zeros(k, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        check(lib().slam_jpeg_encode_batch_dev(ctx.handle, None, ctypes.c_void_p(fr.data_ptr()), k, h, w, ch, w * ch, h * w * ch,
+                                               int(quality), int(sampling), int(restart_interval),
+                                               ctypes.c_void_p(out.data_ptr()), cap, ctypes.c_void_p(sizes.data_ptr()),
+                                               ctypes.c_void_p(status.data_ptr())), ctx.handle)
+        sz = sizes.cpu().numpy()
+        st = status.cpu().numpy()
+        host = out[:, :int(min(sz.max(), cap))].cpu().numpy()
+        return host, sz, st
+
+    host, sz, st = run(frames, h * w * ch + JPEG_ENC_HEADER_ROOM)
+    res = [None if st[i] & L.JPEG_ENC_OVERFLOW else host[i, :int(sz[i])].tobytes() for i in range(n)]
+    again = [i for i in range(n) if res[i] is None]
+    if again:
+        host, sz2, st2 = run(frames[torch.tensor(again, device=dev)].contiguous(), int(sz[again].max()))
+        for k, i in enumerate(again):
+            if st2[k] & L.JPEG_ENC_OVERFLOW:
+                raise L.SlamError(L.SLAM_E_CAPACITY, f"frame {i}: {int(sz2[k])} bytes after a retry sized by the first pass")
+            res[i] = host[k, :int(sz2[k])].tobytes()
+    return res
+
+
+def jpegEncLastTiming(ctx=None):
+    """slam_jpeg_enc_last_timing: ({dct, count, scan, readback, pack, ffcount, write} ms, {frame,
+    coefficient, unstuffed, readback} bytes) of the context's last device encode."""
+    ctx = ctx or default_context()
+    ms = np.zeros(7, np.float64)
+    nb = np.zeros(4, np.uint64)
+    check(lib().slam_jpeg_enc_last_timing(ctx.handle, ptr(ms), ptr(nb)), ctx.handle)
+    return (dict(zip(("dct_ms", "count_ms", "scan_ms", "readback_ms", "pack_ms", "ffcount_ms", "write_ms"), ms.tolist())),
+            dict(zip(("frame_bytes", "coef_bytes", "unstuffed_bytes", "readback_bytes"), [int(v) for v in nb])))

@@ -307,16 +307,43 @@ def write_png(path, frame):
         f.write(chunk(b"IEND", b""))
 
 
-def _write_frame(path, frame):
-    (write_ppm if path.lower().endswith(".ppm") else write_png)(path, frame)
+def write_image(path, frame, ctx=None):
+    """a BGR frame by its name: .jpg / .jpeg through api.imwrite (the device encoder,
+    quality 95, 4:2:0), .ppm as a PPM, anything else as a PNG"""
+    name = path.lower()
+    if name.endswith((".jpg", ".jpeg")):
+        if not api.imwrite(path, np.ascontiguousarray(frame), ctx=ctx):
+            raise OSError(f"cannot write {path}")
+    else:
+        (write_ppm if name.endswith(".ppm") else write_png)(path, frame)
+
+
+
+def write_video(path, global_data, meshes, views, fps=30.0, ctx=None, **render_args):
+    """the views rendered with resident primitives and encoded from the resident frames into one
+    Motion-JPEG AVI (video.VideoWriter); returns the bytes written"""
+    import torch
+    from . import video
+    ctx = ctx or api.default_context()
+    dev = torch.device("cuda", ctx.device)
+    pts, cols, faces, lines, line_cols = scene_primitives(global_data, meshes)
+    prim = [torch.from_numpy(np.ascontiguousarray(a, dt).reshape(-1, k)).to(dev)
+            for a, dt, k in ((pts, np.float32, 3), (cols, np.uint8, 3), (faces, np.int32, 3), (lines, np.float32, 6),
+                             (line_cols, np.uint8, 3))]
+    frames = api.renderViews(*prim, views, ctx=ctx, **render_args)
+    wr = video.VideoWriter(path, "MJPG", fps, (int(frames.shape[2]), int(frames.shape[1])), ctx=ctx)
+    wr.write_batch(frames)
+    return wr.release()
 
 
 def main(config_path, render=None):
     """the onlyViz branch of the reference's main(): reload outputDataDir's
     result files, segment the cloud and write clusters.txt and mesh.ply next to
     them.  render = "view.png" also writes the reference view there (a .ppm name
-    gives a PPM); render = ("fly_%04d.png", "wwwwaadd") writes one frame per key
-    stroke of scene.fly from the reference view.  The default writes nothing more."""
+    gives a PPM, a .jpg name a JPEG from the device encoder); render =
+    ("fly_%04d.png", "wwwwaadd") writes one frame per key stroke of scene.fly from the
+    reference view, and render = ("fly.avi", keys) encodes those frames where they
+    were rendered and writes one Motion-JPEG AVI.  The default writes nothing more."""
     cfg = ConfigService()
     cfg.setConfigFile(config_path)
     if not cfg.getValue("onlyViz"):
@@ -330,13 +357,15 @@ def main(config_path, render=None):
     if render is not None:
         draw = render_scene
         if isinstance(render, str):
-            _write_frame(os.path.join(out_dir, render), draw(gd, meshes)[0])
+            write_image(os.path.join(out_dir, render), draw(gd, meshes)[0])
         else:
             pattern, keys = render
             views = fly(reference_view(gd), keys)
-            if views:
+            if views and pattern.lower().endswith(".avi"):
+                write_video(os.path.join(out_dir, pattern), gd, meshes, views)
+            elif views:
                 for i, frame in enumerate(draw(gd, meshes, views=views)):
-                    _write_frame(os.path.join(out_dir, pattern % i), frame)
+                    write_image(os.path.join(out_dir, pattern % i), frame)
     return segments
 
 

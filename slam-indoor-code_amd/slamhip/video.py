@@ -1,6 +1,6 @@
 """Motion-JPEG video: cv::VideoCapture(path, CAP_OPENCV_MJPEG) over the AVI walker
-(slam_avi_index) and the JPEG decoder, and a minimal AVI writer for already-encoded
-streams.  The reference reads every frame through VideoCapture::read
+(slam_avi_index) and the JPEG decoder, a minimal AVI writer for already-encoded
+streams, and cv::VideoWriter over the JPEG encoder.  The reference reads every frame through VideoCapture::read
 (mainCycleInternals.cpp:107-119); inter-frame codecs are out of scope, and any video
 becomes Motion-JPEG with one transcode."""
 import mmap
@@ -130,8 +130,8 @@ class VideoCapture:
 
 def write_mjpeg_avi(path, jpeg_streams, fps, size):
     """A minimal Motion-JPEG AVI: hdrl (avih, one strl with strh and strf), one movi
-    of 00dc chunks and idx1.  jpeg_streams: the frames, already encoded (there is no
-    encoder here); fps: a number or (rate, scale); size: (width, height).  Returns
+    of 00dc chunks and idx1.  jpeg_streams: the frames, already encoded (VideoWriter
+    below encodes them); fps: a number or (rate, scale); size: (width, height).  Returns
     the number of bytes written."""
     streams = [bytes(s) for s in jpeg_streams]
     w, h = int(size[0]), int(size[1])
@@ -163,3 +163,56 @@ def write_mjpeg_avi(path, jpeg_streams, fps, size):
     with open(path, "wb") as f:
         f.write(data)
     return len(data)
+
+
+class VideoWriter:
+    """cv::VideoWriter(path, fourcc "MJPG", fps, size) over the device JPEG encoder:
+    write(frame) and write_batch(frames) encode (h, w, 3) BGR frames (numpy, or
+    resident torch tensors) with api.imencode_batch, the streams are buffered, and
+    release() writes the file through write_mjpeg_avi.  size: (width, height);
+    restart_rows: a restart interval of that many MCU rows (0: none), which is what
+    the decoder reads fastest.  Deviation: OpenCV's built-in Motion-JPEG writer is an
+    encoder of its own with other arithmetic and its own default quality; this one
+    writes imencode's frames (libjpeg's bytes).  host=True encodes numpy frames with
+    the host encoder instead (the same bytes, no GPU).  A fourcc other than MJPG, or a
+    size that is not positive, leaves the writer closed (isOpened() False)."""
+
+    def __init__(self, path, fourcc="MJPG", fps=30.0, size=None, quality=95, sampling=L.JPEG_420, restart_rows=0, ctx=None, host=False):
+        self.path, self.fps, self.ctx, self.host = path, fps, ctx, bool(host)
+        self.quality, self.sampling, self.restart_rows = int(quality), int(sampling), int(restart_rows)
+        self.size = (int(size[0]), int(size[1])) if size is not None else None
+        self.streams = []
+        name = fourcc.decode() if isinstance(fourcc, bytes) else str(fourcc)
+        self._open = name.upper() == "MJPG" and self.size is not None and min(self.size) > 0 and self.restart_rows >= 0
+        self.bytes_written = 0
+
+    def isOpened(self):
+        return self._open
+
+    def _restart(self):
+        hs = 1 if self.sampling in (L.JPEG_GRAY, L.JPEG_444) else 2
+        return min(self.restart_rows * ((self.size[0] + 8 * hs - 1) // (8 * hs)), 65535)
+
+    def write_batch(self, frames):
+        """encodes (n, h, w, 3) frames in one set of launches and buffers their streams"""
+        if not self._open:
+            raise ValueError("VideoWriter is not open")
+        shape = tuple(int(v) for v in frames.shape)
+        if len(shape) != 4 or shape[1:] != (self.size[1], self.size[0], 3):
+            raise ValueError(f"frames are (n, {self.size[1]}, {self.size[0]}, 3) uint8")
+        if shape[0] and self.host:
+            for f in np.asarray(frames):
+                self.streams.append(api.jpegEncode(f, self.quality, self.sampling, self._restart(), host=True)[0])
+        elif shape[0]:
+            self.streams += api.imencode_batch(frames, self.quality, self.sampling, self._restart(), ctx=self.ctx)
+
+    def write(self, frame):
+        self.write_batch(frame[None])
+
+    def release(self):
+        """writes the file (once); returns the bytes written"""
+        if self._open:
+            self._open = False
+            self.bytes_written = write_mjpeg_avi(self.path, self.streams, self.fps, self.size)
+            self.streams = []
+        return self.bytes_written
