@@ -1105,6 +1105,93 @@ int slam_synth_sequence_dev(slam_ctx* ctx, void* stream, int w, int h, int first
 /* slam_synth_sequence(..., SLAM_SYNTH_DRIFT, ...) */
 int slam_synth_frames(int w, int h, int first, int count, uint64_t seed, uint8_t* out_bgr);
 
+/* ---- dense points: plane-sweep stereo (multi-view densification) ---------------- */
+/* An opt-in stage between the poses and the mesh.  The
+ * definition of every value is tests/mvs_ref.py; the device and the host twin
+ * equal it bit for bit.  Frames are 8-bit with channels 1 or 3 (BGR); gray is the
+ * fixed-point conversion FAST sees.  The reference has no such stage.
+ *
+ * Projection of reference pixel (x, y) into a source at inverse depth w, from the
+ * caller's M (3 x 3 row-major, mathematically K R K^-1) and v (3, K t), in f64 in
+ * this order without contraction:
+ *   q_i = (M[i][0] x + M[i][1] y) + M[i][2],  h_i = q_i + w v[i],  u = h_0 / h_2,  vv = h_1 / h_2,
+ * valid iff h_2 > 0, -0.5 <= u < W - 0.5 and -0.5 <= vv < H - 0.5 (a NaN or an
+ * infinity is invalid), then ix = (int)floor(u + 0.5), iy likewise.
+ *
+ * slam_mvs_census_dev: the 9 x 7 census of nframes resident frames (n x h x w x
+ * channels) into d_out (n x h x w uint64, device): bit b, counted in the order dy
+ * = -3..3 outer, dx = -4..4 inner with the centre skipped, is set iff the gray at
+ * (clamp(x + dx), clamp(y + dy)) is below the centre's; bits 62 and 63 are 0.
+ * One launch; synchronous.  w > 4096: SLAM_E_UNSUPPORTED. */
+int slam_mvs_census_dev(slam_ctx* ctx, void* stream, const uint8_t* d_frames, int nframes, int w, int h, int channels,
+                        uint64_t* d_out);
+/* Depth maps of nref references among nframes resident frames.  Reference i is
+ * frame ref_idx[i] with nsrc[i] (1..4) sources src_idx[4 i ..], their M at M + 36
+ * i + 9 s, v at v + 12 i + 3 s, and D (4..256) inverse depths planes[D i ..].  The
+ * census is computed once per distinct frame of the call.  Per pixel and plane d
+ * the cost of a source is the Hamming distance of the two census words (64 when
+ * the projection is invalid), summed over the (2 radius + 1)^2 window (radius
+ * 0..3, coordinates clamped to the image, every window pixel projected itself)
+ * and over the sources: C[d]; nvalid[d] counts the sources valid at the pixel.
+ * best = the lowest d of minimal C, second = the least C with |d - best| > 1; the
+ * pixel is accepted iff C[best] * 100 < uniq * second (uniq 1..100) and
+ * nvalid[best] >= min_views (1..S).  With a, b, c = C[best - 1], C[best], C[best +
+ * 1], 0 < best < D - 1 and den = a - 2 b + c > 0: off = (double)(a - c) / (double)(2
+ * den), else 0; wq = w[best] + off (w[best + 1] - w[best]) for off >= 0, w[best] +
+ * off (w[best] - w[best - 1]) below (w[best] at the two ends).
+ * Outputs (device, nref x h x w): plane int16 = best, cost int32 = C[best],
+ * inv_depth f32 = (float)wq when accepted, else 0.  The cost volume is never
+ * stored.  Synchronous.  S outside 1..4, D outside 4..256, radius > 3, uniq or
+ * min_views out of range, an index outside the frames, or a non-finite M, v or
+ * plane: SLAM_E_INVALID_ARG; w > 4096: SLAM_E_UNSUPPORTED.  Huge finite values are
+ * legal and come out invalid. */
+int slam_mvs_depth_batch_dev(slam_ctx* ctx, void* stream, const uint8_t* d_frames, int nframes, int w, int h,
+                             int channels, int nref, const int32_t* ref_idx, const int32_t* nsrc,
+                             const int32_t* src_idx, const double* M, const double* v, const double* planes, int D,
+                             int radius, int uniq, int min_views, int16_t* d_plane, int32_t* d_cost,
+                             float* d_inv_depth);
+/* Pairwise consistency filter and point emission over nmaps depth maps
+ * (d_inv_depth: nmaps x h x w f32, device); map i belongs to frame frame_idx[i]
+ * and lists nnbr[i] (0..4) neighbour maps nbr_idx[4 i ..] with M and v of the
+ * motion map i -> neighbour, laid out as above.  A pixel with wi = inv_depth > 0
+ * is consistent with neighbour j iff its projection at w = (double)wi is valid,
+ * wj (the neighbour's value at the nearest pixel) > 0 and fabs(h_2 (double)wj /
+ * (double)wi - 1.0) <= eps.  It is kept iff its consistent count >= min_consistent
+ * (0..4), x % step == 0 and y % step == 0, and it lies outside the radius + 4
+ * border.  Survivors leave in raster order, map after map: points (host, cap x 3
+ * f64) X = c + (B (x, y, 1)) * (1.0 / (double)wi) with B (9) and c (3) of map i at B
+ * + 9 i and c + 3 i, evaluated as ((B[k][0] x + B[k][1] y) + B[k][2]); colors
+ * (host, cap x 3) the frame's BGR bytes (gray three times for one channel).
+ * *n_out = the number of survivors; SLAM_E_CAPACITY when it exceeds cap (nothing
+ * written).  Synchronous. */
+int slam_mvs_fuse_dev(slam_ctx* ctx, void* stream, const uint8_t* d_frames, int nframes, int w, int h, int channels,
+                      int nmaps, const int32_t* frame_idx, const float* d_inv_depth, const int32_t* nnbr,
+                      const int32_t* nbr_idx, const double* M, const double* v, const double* B, const double* c,
+                      double eps, int min_consistent, int step, int radius, double* points, uint8_t* colors, int cap,
+                      int* n_out);
+/* slam_mvs_depth_batch_dev for one reference and its S sources in host memory
+ * (rows `step` bytes apart); M (S x 9), v (S x 3), planes (D); outputs h x w in
+ * host memory. */
+int slam_mvs_depth(slam_ctx* ctx, const uint8_t* ref, const uint8_t* const* srcs, int S, int w, int h, size_t step,
+                   int channels, const double* M, const double* v, const double* planes, int D, int radius, int uniq,
+                   int min_views, int16_t* plane, int32_t* cost, float* inv_depth);
+/* slam_mvs_fuse_dev for nmaps host frames (frames[i] is map i's) and host maps
+ * (inv_depth: nmaps x h x w). */
+int slam_mvs_fuse(slam_ctx* ctx, const uint8_t* const* frames, int w, int h, size_t step, int channels, int nmaps,
+                  const float* inv_depth, const int32_t* nnbr, const int32_t* nbr_idx, const double* M, const double* v,
+                  const double* B, const double* c, double eps, int min_consistent, int step_px, int radius,
+                  double* points, uint8_t* colors, int cap, int* n_out);
+/* HIP-event times (ms) of the kernels of the context's last slam_mvs_depth_batch_dev
+ * (ms[0] mvs_census, ms[1] mvs_sweep, every launch of the call) and of its last
+ * slam_mvs_fuse_dev (ms[2] mvs_filter + mvs_count, ms[3] mvs_emit; 0 when nothing
+ * survived); 0 before the first call. */
+int slam_mvs_last_timing(slam_ctx* ctx, double* ms);
+/* The host twin of slam_mvs_depth: no context, no device, the same arithmetic
+ * (csrc/mvs_math.h) on up to 16 threads, the same results bit for bit. */
+int slam_mvs_depth_host(const uint8_t* ref, const uint8_t* const* srcs, int S, int w, int h, size_t step, int channels,
+                        const double* M, const double* v, const double* planes, int D, int radius, int uniq,
+                        int min_views, int16_t* plane, int32_t* cost, float* inv_depth);
+
 #ifdef __cplusplus
 }
 #endif

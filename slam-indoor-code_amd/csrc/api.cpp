@@ -425,7 +425,8 @@ void slam_destroy(slam_ctx* c)
                       &c->klt_img, &c->klt_pyr, &c->klt_deriv, &c->klt_pts,
                       &c->jpeg_in, &c->jpeg_coef, &c->jpeg_planes, &c->jpeg_out, &c->jpeg_sync,
                       &c->jenc_ws, &c->jenc_coef, &c->jenc_bits, &c->jenc_ff, &c->jenc_io,
-                      &c->render_ws, &c->render_in, &c->render_out};
+                      &c->render_ws, &c->render_in, &c->render_out,
+                      &c->mvs_census, &c->mvs_par, &c->mvs_mask, &c->mvs_out, &c->mvs_in};
     for (DevBuf* b : bufs) b->release();
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->ev_up) (void)hipEventDestroy(c->ev_up);
@@ -440,6 +441,7 @@ void slam_destroy(slam_ctx* c)
     jpeg_release(c);
     jpeg_enc_release(c);
     render_release(c);
+    mvs_release(c);
     for (auto& f : c->prof)
         for (hipEvent_t e : f.ev) (void)hipEventDestroy(e);
     if (c->ev_sync) (void)hipEventDestroy(c->ev_sync);

@@ -339,6 +339,11 @@ struct slam_ctx {
     unsigned long long render_in_count = 0;   // views x primitives of the last call
     std::vector<hipEvent_t> render_evs;   // five per chunk of views of the largest call so far
     double render_ms[4] = {0, 0, 0, 0};   // clear, points + lines, triangles, resolve
+    // plane-sweep stereo (mvs.hip): the census maps of a call's distinct frames, the parameter block,
+    // the filter's masks, slam_mvs_fuse_dev's device result, the staged host frames + maps of the host-pointer calls
+    slamhip::DevBuf mvs_census, mvs_par, mvs_mask, mvs_out, mvs_in;
+    hipEvent_t mvs_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    double mvs_ms[4] = {0, 0, 0, 0};      // slam_mvs_last_timing: census, sweep, filter + count, emit
 
     bool prof_on = false;
     slamhip::ProfFamily prof[slamhip::kProfFamilies];
@@ -660,6 +665,9 @@ void jpeg_release(slam_ctx* c);
 // ---- JPEG encoding (jpeg_enc.hip) ----
 void jpeg_enc_release(slam_ctx* c);
 
+// ---- plane-sweep stereo (mvs.hip) ----
+// destroys the context's timing events
+void mvs_release(slam_ctx* c);
 // ---- scene rendering (render.hip) ----
 // destroys the context's render events
 void render_release(slam_ctx* c);

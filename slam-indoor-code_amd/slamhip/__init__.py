@@ -32,7 +32,9 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
                   imencode, imwrite, imencode_batch, jpegEncode, jpegEncodeBound, jpegEncLastTiming,
                   IMWRITE_JPEG_QUALITY, IMWRITE_JPEG_RST_INTERVAL, IMWRITE_JPEG_SAMPLING_FACTOR,
                   IMWRITE_JPEG_SAMPLING_FACTOR_420, IMWRITE_JPEG_SAMPLING_FACTOR_422, IMWRITE_JPEG_SAMPLING_FACTOR_444,
-                  renderViews, renderCamera, renderStats)
+                  renderViews, renderCamera, renderStats,
+                  censusTransform, planeSweepDepth, planeSweepDepthBatch, fuseDepthMaps)
+from .dense import DenseParams, densify, depth_planes, sweep_matrices
 from .video import VideoCapture, VideoWriter, write_mjpeg_avi
 from .config import ConfigError, ConfigService, reference_example
 from .calibration import CalibrationError, chessboard_photos_calibration

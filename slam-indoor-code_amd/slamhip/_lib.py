@@ -208,6 +208,14 @@ SIGNATURES = {
     "slam_render_views_dev": (_I, [_P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _I]),
     "slam_render": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     "slam_render_last_stats": (_I, [_P, _P, _P]),
+    "slam_mvs_census_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "slam_mvs_depth_batch_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "slam_mvs_fuse_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _D, _I, _I, _I, _P, _P, _I,
+                               _P]),
+    "slam_mvs_depth": (_I, [_P, _P, _P, _I, _I, _I, _SZ, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "slam_mvs_fuse": (_I, [_P, _P, _I, _I, _SZ, _I, _I, _P, _P, _P, _P, _P, _P, _P, _D, _I, _I, _I, _P, _P, _I, _P]),
+    "slam_mvs_last_timing": (_I, [_P, _P]),
+    "slam_mvs_depth_host": (_I, [_P, _P, _I, _I, _I, _SZ, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
 }
 
 _lib = None

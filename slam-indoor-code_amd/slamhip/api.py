@@ -1718,3 +1718,159 @@ def jpegEncLastTiming(ctx=None):
     check(lib().slam_jpeg_enc_last_timing(ctx.handle, ptr(ms), ptr(nb)), ctx.handle)
     return (dict(zip(("dct_ms", "count_ms", "scan_ms", "readback_ms", "pack_ms", "ffcount_ms", "write_ms"), ms.tolist())),
             dict(zip(("frame_bytes", "coef_bytes", "unstuffed_bytes", "readback_bytes"), [int(v) for v in nb])))
+
+
+# ---- dense points: plane-sweep stereo ------------------------
+
+def _mvs_frames(frames):
+    """host frames of one shape as contiguous arrays -> (list, w, h, channels)"""
+    out = [np.ascontiguousarray(_frame13(f)[0]) for f in frames]
+    a = out[0]
+    if any(f.shape != a.shape for f in out):
+        raise ValueError("frames of one shape")
+    return out, a.shape[1], a.shape[0], 1 if a.ndim == 2 else 3
+
+
+def _ptr_array(arrays):
+    return (ctypes.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+
+
+def censusTransform(frame, ctx=None):
+    """the 9 x 7 census of a frame (slam_mvs_census_dev): 62 bits in a uint64, bit
+    b in the order dy = -3..3 outer, dx = -4..4 inner, centre skipped, set iff the
+    clamped neighbour's gray is below the centre's.  `frame`: a host array -> (h,
+    w) uint64, or a resident torch batch (n, h, w[, 3]) -> (n, h, w) uint64."""
+    import torch
+    c = _ctx(ctx)
+    single = isinstance(frame, np.ndarray)
+    if single:
+        a = np.ascontiguousarray(_frame13(frame)[0])
+        frame = torch.from_numpy(a[None]).cuda()
+    fr, n, w, h, ch = _resident(frame)
+    out = torch.empty((n, h, w), dtype=torch.int64, device=fr.device)
+    check(lib().slam_mvs_census_dev(c, None, ctypes.c_void_p(fr.data_ptr()), n, w, h, ch, ctypes.c_void_p(out.data_ptr())), c)
+    res = out.cpu().numpy().view(np.uint64)
+    return res[0] if single else res
+
+
+def _mvs_pose_args(M, v, planes, S):
+    M = np.ascontiguousarray(M, np.float64).reshape(S, 9)
+    v = np.ascontiguousarray(v, np.float64).reshape(S, 3)
+    planes = np.ascontiguousarray(planes, np.float64).reshape(-1)
+    return M, v, planes
+
+
+def planeSweepDepth(ref, srcs, M, v, planes, radius=2, uniq=80, min_views=1, ctx=None, host=False):
+    """Plane-sweep depth of one reference frame against S = len(srcs) sources (host
+    arrays of one shape): slam_mvs_depth, or with host=True its twin
+    slam_mvs_depth_host, which needs no device and gives the same bits.  M (S, 3, 3)
+    and v (S, 3) as dense.sweep_matrices returns them, planes (D) inverse depths.
+    Returns (plane int16, cost int32, inv_depth float32), each (h, w); inv_depth is
+    0 where the winner was rejected."""
+    fr, w, h, ch = _mvs_frames([ref] + list(srcs))
+    S = len(fr) - 1
+    M, v, planes = _mvs_pose_args(M, v, planes, S) if S > 0 else (np.zeros((0, 9)), np.zeros((0, 3)),
+                                                                  np.ascontiguousarray(planes, np.float64).reshape(-1))
+    plane = np.empty((h, w), np.int16)
+    cost = np.empty((h, w), np.int32)
+    inv = np.empty((h, w), np.float32)
+    sp = _ptr_array(fr[1:]) if S > 0 else None
+    tail = (S, w, h, w * ch, ch, ptr(M), ptr(v), ptr(planes), len(planes), int(radius), int(uniq), int(min_views),
+            ptr(plane), ptr(cost), ptr(inv))
+    if host:
+        check(lib().slam_mvs_depth_host(ptr(fr[0]), sp, *tail))
+    else:
+        c = _ctx(ctx)
+        check(lib().slam_mvs_depth(c, ptr(fr[0]), sp, *tail), c)
+    return plane, cost, inv
+
+
+def planeSweepDepthBatch(frames, ref_idx, src_idx, M, v, planes, radius=2, uniq=80, min_views=1, ctx=None):
+    """slam_mvs_depth_batch_dev: depth maps of the references ref_idx among the
+    resident frames (a torch batch (n, h, w[, 3])); src_idx[i] lists reference i's 1..4
+    sources, M (nref, 4, 9) and v (nref, 4, 3) hold their matrices (unused rows
+    ignored), planes (nref, D).  The census runs once per distinct frame.  Returns
+    resident (plane int16, cost int32, inv_depth float32) tensors, each (nref, h, w)."""
+    import torch
+    c = _ctx(ctx)
+    fr, n, w, h, ch = _resident(frames)
+    nref = len(ref_idx)
+    ref = np.ascontiguousarray(ref_idx, np.int32).reshape(nref)
+    nsrc = np.array([len(s) for s in src_idx], np.int32)
+    src = np.full((nref, 4), -1, np.int32)
+    for i, s in enumerate(src_idx):
+        if len(s) > 4:
+            raise ValueError("at most 4 sources per reference")
+        src[i, :len(s)] = s
+    M = np.ascontiguousarray(M, np.float64).reshape(nref, 36)
+    v = np.ascontiguousarray(v, np.float64).reshape(nref, 12)
+    planes = np.ascontiguousarray(planes, np.float64).reshape(nref, -1)
+    plane = torch.empty((nref, h, w), dtype=torch.int16, device=fr.device)
+    cost = torch.empty((nref, h, w), dtype=torch.int32, device=fr.device)
+    inv = torch.empty((nref, h, w), dtype=torch.float32, device=fr.device)
+    check(lib().slam_mvs_depth_batch_dev(c, None, ctypes.c_void_p(fr.data_ptr()), n, w, h, ch, nref, ptr(ref), ptr(nsrc),
+                                         ptr(src), ptr(M), ptr(v), ptr(planes), planes.shape[1], int(radius), int(uniq),
+                                         int(min_views), ctypes.c_void_p(plane.data_ptr()),
+                                         ctypes.c_void_p(cost.data_ptr()), ctypes.c_void_p(inv.data_ptr())), c)
+    return plane, cost, inv
+
+
+def fuseDepthMaps(frames, inv_depth, nbrs, M, v, B, c, eps=0.01, min_consistent=1, step=4, radius=2, frame_idx=None,
+                  cap=None, ctx=None):
+    """slam_mvs_fuse_dev / slam_mvs_fuse: the pairwise consistency filter over nmaps
+    depth maps and the emission of the survivors, raster order, map after map.
+    frames: a resident torch batch (map i belongs to frame frame_idx[i], default i)
+    with inv_depth a resident (nmaps, h, w) float32 tensor, or a list of host frames
+    with host maps.  nbrs[i]: the maps map i is checked against (at most 4), M
+    (nmaps, 4, 9) / v (nmaps, 4, 3) the motions map i -> neighbour, B (nmaps, 9) and c
+    (nmaps, 3) the back-projection (dense.backproject_matrices).  cap: the output
+    capacity (default: every grid pixel); too small raises SlamError with code
+    SLAM_E_CAPACITY and the needed count in its `needed`.  Returns (points (n, 3)
+    float64, colors (n, 3) uint8)."""
+    h_ctx = _ctx(ctx)
+    nmaps = len(nbrs)
+    nn = np.array([len(r) for r in nbrs], np.int32)
+    nb = np.full((max(nmaps, 1), 4), -1, np.int32)
+    for i, r in enumerate(nbrs):
+        if len(r) > 4:
+            raise ValueError("at most 4 neighbours per map")
+        nb[i, :len(r)] = r
+    M = np.ascontiguousarray(M, np.float64).reshape(nmaps, 36)
+    v = np.ascontiguousarray(v, np.float64).reshape(nmaps, 12)
+    B = np.ascontiguousarray(B, np.float64).reshape(nmaps, 9)
+    cc = np.ascontiguousarray(c, np.float64).reshape(nmaps, 3)
+    resident = not isinstance(frames, (list, tuple, np.ndarray)) and hasattr(frames, "data_ptr")
+    if resident:
+        fr, n, w, h, ch = _resident(frames)
+    else:
+        fl, w, h, ch = _mvs_frames(list(frames))
+    if cap is None:
+        cap = nmaps * (-(-h // step)) * (-(-w // step))
+    pts = np.empty((max(cap, 1), 3), np.float64)
+    cols = np.empty((max(cap, 1), 3), np.uint8)
+    n_out = ctypes.c_int(0)
+    if resident:
+        import torch
+        fi = np.ascontiguousarray(np.arange(nmaps) if frame_idx is None else frame_idx, np.int32).reshape(nmaps)
+        inv = inv_depth if hasattr(inv_depth, "data_ptr") else torch.from_numpy(np.ascontiguousarray(inv_depth, np.float32)).to(fr.device)
+        if inv.dtype != torch.float32 or tuple(inv.shape) != (nmaps, h, w):
+            raise ValueError("inv_depth: float32 (nmaps, h, w)")
+        inv = inv.contiguous()
+        torch.cuda.current_stream(inv.device).synchronize()
+        rc = lib().slam_mvs_fuse_dev(h_ctx, None, ctypes.c_void_p(fr.data_ptr()), n, w, h, ch, nmaps, ptr(fi),
+                                     ctypes.c_void_p(inv.data_ptr()), ptr(nn), ptr(nb), ptr(M), ptr(v), ptr(B), ptr(cc),
+                                     float(eps), int(min_consistent), int(step), int(radius), ptr(pts), ptr(cols), int(cap),
+                                     ctypes.byref(n_out))
+    else:
+        if len(fl) != nmaps:
+            raise ValueError("one host frame per map")
+        inv = np.ascontiguousarray(inv_depth, np.float32).reshape(nmaps, h, w)
+        rc = lib().slam_mvs_fuse(h_ctx, _ptr_array(fl), w, h, w * ch, ch, nmaps, ptr(inv), ptr(nn), ptr(nb), ptr(M), ptr(v),
+                                 ptr(B), ptr(cc), float(eps), int(min_consistent), int(step), int(radius), ptr(pts),
+                                 ptr(cols), int(cap), ctypes.byref(n_out))
+    try:
+        check(rc, h_ctx)
+    except L.SlamError as e:
+        e.needed = n_out.value          # SLAM_E_CAPACITY: the count that did not fit
+        raise
+    return pts[:n_out.value].copy(), cols[:n_out.value].copy()

@@ -987,8 +987,11 @@ class Logs:
             self.poses = open(os.path.join(out_dir, "poses.txt"), "w")
             self.rotations = open(os.path.join(out_dir, "rotations.txt"), "w")
         self.pose_list, self.rotation_list = [], []
+        self.frames = None       # slam_main(dense=...): the good frame of every logged pose
 
-    def pose(self, R, t):
+    def pose(self, R, t, frame=None):
+        if self.frames is not None:
+            self.frames.append(frame)
         self.pose_list.append(np.asarray(t, np.float64).reshape(3).copy())
         self.rotation_list.append(np.asarray(R, np.float64).reshape(3, 3).copy())
         if self.poses:
@@ -1307,7 +1310,7 @@ def move_processed_data_to_global_struct(processed, gd):
 
 # ---- mainCycle.cpp -------------------------------------------------------------
 
-def define_first_pair_frames(cond, media, batch, deque, ops):
+def define_first_pair_frames(cond, media, batch, deque, ops, keep_first=False):
     first = find_first_good_frame(media, cond, deque[0], ops)
     if first is None:
         return EMPTY_BATCH, None
@@ -1318,6 +1321,8 @@ def define_first_pair_frames(cond, media, batch, deque, ops):
         if idx >= 0:
             deque[1].allExtractedFeatures = feats
             deque[1].allMatches = drop_invalid_matches(deque[0], deque[1], matches)
+            if keep_first:
+                deque[0].first_frame = first     # the frame of the pair's first pose (slam_main(dense=...))
             return idx, frame
         first = batch[0].frame
         deque[0].allExtractedFeatures = batch[0].features.copy()
@@ -1325,7 +1330,7 @@ def define_first_pair_frames(cond, media, batch, deque, ops):
 
 
 def processing_first_pair_frames(media, K, cond, batch, deque, gd, logs, ops):
-    idx, second = define_first_pair_frames(cond, media, batch, deque, ops)
+    idx, second = define_first_pair_frames(cond, media, batch, deque, ops, keep_first=logs.frames is not None)
     if idx == EMPTY_BATCH:
         return EMPTY_BATCH, None
     p1, p2, mask = compute_transformation_and_filter_points(cond, K, deque[0], deque[1], ops)
@@ -1344,8 +1349,8 @@ def main_cycle(media, K, cond, deque, gd, logs, ops, stats=None):
         return EMPTY_BATCH
     processed.append(deque[0].snapshot())
     processed.append(deque[1].snapshot())
-    logs.pose(deque[0].rotation, deque[0].motion)
-    logs.pose(deque[1].rotation, deque[1].motion)
+    logs.pose(deque[0].rotation, deque[0].motion, getattr(deque[0], "first_frame", None))
+    logs.pose(deque[1].rotation, deque[1].motion, last_good)
 
     last = 1
     bidx = FRAME_NOT_FOUND
@@ -1372,7 +1377,7 @@ def main_cycle(media, K, cond, deque, gd, logs, ops, stats=None):
         found, rvec, tvec = ops.solve_pnp(obj, img, K)
         nxt.motion = np.asarray(tvec, np.float64).reshape(3, 1).copy()
         nxt.rotation = ops.rodrigues(rvec)
-        logs.pose(nxt.rotation, nxt.motion)
+        logs.pose(nxt.rotation, nxt.motion, frame)
 
         p1, p2 = key_point_coords(prev.allExtractedFeatures, nxt.allExtractedFeatures, nxt.allMatches,
                                   prev.undistorted, nxt.undistorted)
@@ -1472,7 +1477,7 @@ def define_camera_position(old_deque, last_id, fd):
 
 
 def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK=None, undistort="frames",
-              criteria=(50, 0.01), max_residual=0.01, tracker=None, klt=None, lens_model=None):
+              criteria=(50, 0.01), max_residual=0.01, tracker=None, klt=None, lens_model=None, dense=None):
     """src/main.cpp:71-107 slamMain: mainCycle restarts from the last pose until
     the sequence ends, then points.txt / colors.txt.  K (3x3 float64) is
     updated in place by BA, as the reference's calibrationMatrix is.  dist: the
@@ -1506,7 +1511,16 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
     unchanged.  The winner's features are its surviving tracked positions
     followed by its own FAST keypoints away from them, its matches the tracks
     (tracked_features).  Everything downstream is untouched.  Not combined with
-    dist.  Returns (GlobalData, Logs)."""
+    dist.
+
+    dense (opt-in; a dense.DenseParams, None changes and keeps nothing): the good
+    frame of every logged pose is kept (logs.frames), and after the last cycle
+    dense.densify runs plane-sweep stereo over them with the final rotations and
+    positions (after BA) and the sparse cloud's depth range; the points go to
+    gd.densePoints / gd.denseColors and, with out_dir, to dense_points.txt /
+    dense_colors.txt in rawOutput's format.  The four result files are unchanged.
+    A frame count that differs from the pose count raises.
+    Returns (GlobalData, Logs)."""
     if undistort not in ("frames", "points"):
         raise ValueError('undistort: "frames" or "points"')
     if tracker not in (None, "klt"):
@@ -1527,6 +1541,8 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
     if tracker is not None:
         cond.tracker = klt or KltParams()
     logs = Logs(out_dir if out_dir is not None else None)
+    if dense is not None:
+        logs.frames = []
     gd = GlobalData()
     old, last_id = [], -1
     prefetch = getattr(ops, "prefetched", None)
@@ -1550,4 +1566,18 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
         if prefetch is not None:
             media.close()
     logs.close(gd)
+    if dense is not None:
+        from .dense import densify
+        if len(logs.frames) != len(gd.cameraRotations) or len(logs.frames) != len(gd.spatialCameraPositions) \
+                or any(f is None for f in logs.frames):
+            raise RuntimeError(f"dense: {len(logs.frames)} good frames kept for {len(gd.cameraRotations)} final poses")
+        gd.densePoints, gd.denseColors = densify(logs.frames, K, gd.cameraRotations, gd.spatialCameraPositions,
+                                                 gd.spatialPoints, dense, ctx=getattr(ops, "ctx", None))
+        if logs.out_dir:
+            with open(os.path.join(logs.out_dir, "dense_points.txt"), "w") as f:
+                if len(gd.densePoints):
+                    raw_output(gd.densePoints, f)
+            with open(os.path.join(logs.out_dir, "dense_colors.txt"), "w") as f:
+                if len(gd.denseColors):
+                    raw_output(gd.denseColors, f)
     return gd, logs

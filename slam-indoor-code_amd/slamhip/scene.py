@@ -61,18 +61,23 @@ def _rows(path, width):
     return v[:len(v) // width * width].reshape(-1, width)
 
 
-def load_global_data(out_dir):
+def load_global_data(out_dir, cloud="sparse"):
     """IOmisc.cpp:133-177: GlobalData from points.txt, colors.txt, poses.txt and
     rotations.txt of `out_dir` as cycle.Logs writes them (rawOutput rows).
     Colours are cast with (uchar), i.e. truncated.  Raises ValueError where the
-    reference throws: rotation / pose counts or point / colour counts differ."""
+    reference throws: rotation / pose counts or point / colour counts differ.
+    cloud="dense" reads dense_points.txt / dense_colors.txt (slam_main(dense=...))
+    in place of the sparse cloud's files."""
+    if cloud not in ("sparse", "dense"):
+        raise ValueError('cloud: "sparse" or "dense"')
+    prefix = "dense_" if cloud == "dense" else ""
     poses = _rows(os.path.join(out_dir, "poses.txt"), 3)
     rotations = _rows(os.path.join(out_dir, "rotations.txt"), 9)
     if len(rotations) != len(poses):
         raise ValueError("Count of rotations and translations must be equal: "
                          f"{len(rotations)} rotations, {len(poses)} translations")
-    points = _rows(os.path.join(out_dir, "points.txt"), 3)
-    colors = _rows(os.path.join(out_dir, "colors.txt"), 3)
+    points = _rows(os.path.join(out_dir, prefix + "points.txt"), 3)
+    colors = _rows(os.path.join(out_dir, prefix + "colors.txt"), 3)
     if len(points) != len(colors):
         raise ValueError("Count of points and their colors must be equal: "
                          f"{len(points)} points, {len(colors)} colors")
@@ -336,20 +341,21 @@ def write_video(path, global_data, meshes, views, fps=30.0, ctx=None, **render_a
     return wr.release()
 
 
-def main(config_path, render=None):
+def main(config_path, render=None, cloud="sparse"):
     """the onlyViz branch of the reference's main(): reload outputDataDir's
     result files, segment the cloud and write clusters.txt and mesh.ply next to
     them.  render = "view.png" also writes the reference view there (a .ppm name
     gives a PPM, a .jpg name a JPEG from the device encoder); render =
     ("fly_%04d.png", "wwwwaadd") writes one frame per key stroke of scene.fly from the
     reference view, and render = ("fly.avi", keys) encodes those frames where they
-    were rendered and writes one Motion-JPEG AVI.  The default writes nothing more."""
+    were rendered and writes one Motion-JPEG AVI.  The default writes nothing more.
+    cloud="dense" works on the dense cloud of slam_main(dense=...) instead."""
     cfg = ConfigService()
     cfg.setConfigFile(config_path)
     if not cfg.getValue("onlyViz"):
         raise ValueError("scene.main handles onlyViz = true; run cycle.slam_main first, then scene.segment")
     out_dir = cfg.getValue("outputDataDir")
-    gd = load_global_data(out_dir)
+    gd = load_global_data(out_dir, cloud)
     segments = segment(gd, cfg)
     write_clusters(segments, os.path.join(out_dir, "clusters.txt"))
     meshes = mesh(segments)
