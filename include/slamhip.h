@@ -1192,6 +1192,69 @@ int slam_mvs_depth_host(const uint8_t* ref, const uint8_t* const* srcs, int S, i
                         const double* M, const double* v, const double* planes, int D, int radius, int uniq,
                         int min_views, int16_t* plane, int32_t* cost, float* inv_depth);
 
+/* ---- place recognition: a flat visual vocabulary and bag-of-words retrieval (place.hip) ----
+ * All arithmetic is integer except the one IEEE division of a score, so device,
+ * host twin and the numpy contract (tests/place_ref.py) agree bit for bit.
+ * kind: SLAM_VOC_SIFT rows of 128 u8 compared by squared L2 (the whole u8 range is
+ * legal, d^2 up to 128 * 255^2), SLAM_VOC_ORB rows of 32 bytes compared by Hamming
+ * distance.  Limits: 1 <= K <= 65536 words, at most 2^24 descriptors per call, at
+ * most 65535 descriptors per image, idf weights in [0, 1023], k <= 32.  A bad size,
+ * an unknown kind, a weight out of range or too many descriptors in an image is
+ * SLAM_E_INVALID_ARG; none of them reads or writes out of bounds.  Device pointers
+ * of descriptors and centroids are 16-byte aligned.  Every call is synchronous. */
+enum { SLAM_VOC_SIFT = 0, SLAM_VOC_ORB = 1 };
+/* word[i] = the centroid (row of d_cent, K x B bytes) with the least distance to
+ * descriptor i (d_desc, n x B bytes), ties to the lowest centroid index; dist[i] =
+ * that distance.  n = 0 is legal and writes nothing. */
+int slam_voc_assign_dev(slam_ctx* ctx, void* stream, const uint8_t* d_desc, int n, const uint8_t* d_cent, int K,
+                        int kind, int32_t* d_word, int32_t* d_dist);
+/* Lloyd's algorithm in integers: d_cent[c] = d_desc[floor(c n / K)], then at most
+ * `iters` times: assign, then for every non-empty cluster of count n_c the new
+ * centroid is floor((2 S + n_c) / (2 n_c)) per dimension (SIFT, S the integer sum)
+ * or bit = (2 ones > n_c) (ORB); an empty cluster keeps its centroid.  Stops after
+ * an iteration that changes no centroid; *iters_run (host) = iterations performed.
+ * 1 <= n; iters >= 0.  Only the changed flag is read back per iteration. */
+int slam_voc_train_dev(slam_ctx* ctx, void* stream, const uint8_t* d_desc, int n, int K, int iters, int kind,
+                       uint8_t* d_cent, int32_t* iters_run);
+/* tf-idf vectors of m images: image r owns the words d_word[offsets[r] ..
+ * offsets[r + 1]) (offsets: host, m + 1 ascending values); h_k counts its words,
+ * d_vec[r K + k] = h_k weights[k] (u32) and d_total[r] = sum_k of them (u64).
+ * weights: host, K values.  An image without descriptors gives the zero vector;
+ * a word outside [0, K) in device memory is ignored. */
+int slam_bow_vectors_dev(slam_ctx* ctx, void* stream, const int32_t* d_word, const int32_t* offsets, int m,
+                         const int32_t* weights, int K, uint32_t* d_vec, uint64_t* d_total);
+/* d_scores[i m + r] = score of query i (d_q: nq x K, d_qtotal) against database
+ * row r (d_db: m x K, d_dbtotal): num = sum_k min(a_k B, b_k A) in int64 (exact:
+ * at most A B <= 2^52), score = (double)num / ((double)A (double)B), 0.0 when A or
+ * B is 0 -- the histogram intersection of the L1-normalised vectors. */
+int slam_bow_score_dev(slam_ctx* ctx, void* stream, const uint32_t* d_q, const uint64_t* d_qtotal, int nq,
+                       const uint32_t* d_db, const uint64_t* d_dbtotal, int m, int K, double* d_scores);
+/* For each of nq rows of d_scores (m values each): the k best columns of [first,
+ * last) by (score descending, index ascending) into d_idx / d_score (nq x k),
+ * padded with index -1 and score 0.0.  0 <= first <= last <= m, 1 <= k <= 32. */
+int slam_bow_topk_dev(slam_ctx* ctx, void* stream, const double* d_scores, int nq, int m, int first, int last, int k,
+                      int32_t* d_idx, double* d_score);
+/* The same calls on host buffers (staged through the context's workspace);
+ * slam_bow_vectors also refuses a word outside [0, K); slam_bow_query is the score
+ * followed by the top-k. */
+int slam_voc_assign(slam_ctx* ctx, const uint8_t* desc, int n, const uint8_t* cent, int K, int kind, int32_t* word,
+                    int32_t* dist);
+int slam_voc_train(slam_ctx* ctx, const uint8_t* desc, int n, int K, int iters, int kind, uint8_t* cent,
+                   int32_t* iters_run);
+int slam_bow_vectors(slam_ctx* ctx, const int32_t* word, const int32_t* offsets, int m, const int32_t* weights, int K,
+                     uint32_t* vec, uint64_t* total);
+int slam_bow_query(slam_ctx* ctx, const uint32_t* q, const uint64_t* qtotal, int nq, const uint32_t* db,
+                   const uint64_t* dbtotal, int m, int K, int first, int last, int k, int32_t* idx, double* score);
+/* The host twins: no context, no device, the same arithmetic (csrc/place_math.h)
+ * on up to 16 threads, the same results bit for bit. */
+int slam_voc_assign_host(const uint8_t* desc, int n, const uint8_t* cent, int K, int kind, int32_t* word,
+                         int32_t* dist);
+int slam_voc_train_host(const uint8_t* desc, int n, int K, int iters, int kind, uint8_t* cent, int32_t* iters_run);
+int slam_bow_vectors_host(const int32_t* word, const int32_t* offsets, int m, const int32_t* weights, int K,
+                          uint32_t* vec, uint64_t* total);
+int slam_bow_score_host(const uint32_t* q, const uint64_t* qtotal, int nq, const uint32_t* db, const uint64_t* dbtotal,
+                        int m, int K, double* scores);
+
 #ifdef __cplusplus
 }
 #endif

@@ -344,6 +344,10 @@ struct slam_ctx {
     slamhip::DevBuf mvs_census, mvs_par, mvs_mask, mvs_out, mvs_in;
     hipEvent_t mvs_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     double mvs_ms[4] = {0, 0, 0, 0};      // slam_mvs_last_timing: census, sweep, filter + count, emit
+    // place recognition (place.hip): the assign partials of the K splits, the centroid norms, training's
+    // words + distances + sorted order, its counts + starts + cursors + changed flag, the uploaded
+    // offsets + weights, the staged buffers of the host-pointer calls
+    slamhip::DevBuf place_part, place_norm, place_word, place_cnt, place_par, place_in;
 
     bool prof_on = false;
     slamhip::ProfFamily prof[slamhip::kProfFamilies];
@@ -668,6 +672,13 @@ void jpeg_enc_release(slam_ctx* c);
 // ---- plane-sweep stereo (mvs.hip) ----
 // destroys the context's timing events
 void mvs_release(slam_ctx* c);
+// ---- place recognition (place.hip, place_host.cpp) ----
+// argument checks shared by the device entry points and the host twins (place_host.cpp)
+int place_check_assign(const void* desc, int n, const void* cent, int K, int kind);
+int place_check_train(const void* desc, int n, int K, int iters, int kind, const void* cent, const void* iters_run);
+int place_check_vectors(const int32_t* offsets, int m, const int32_t* weights, int K);
+int place_check_score(int nq, int m, int K);
+int place_check_topk(int nq, int m, int first, int last, int k);
 // ---- scene rendering (render.hip) ----
 // destroys the context's render events
 void render_release(slam_ctx* c);

@@ -35,6 +35,8 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
                   renderViews, renderCamera, renderStats,
                   censusTransform, planeSweepDepth, planeSweepDepthBatch, fuseDepthMaps)
 from .dense import DenseParams, densify, depth_planes, sweep_matrices
+from .place import Database, LoopParams, Vocabulary, detect_loops, verify_loop
+from . import place
 from .video import VideoCapture, VideoWriter, write_mjpeg_avi
 from .config import ConfigError, ConfigService, reference_example
 from .calibration import CalibrationError, chessboard_photos_calibration

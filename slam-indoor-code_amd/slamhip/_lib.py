@@ -49,6 +49,7 @@ KLT_MAX_LEVELS = 9                                     # maxLevel 0..8
 JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = 0, 0x11, 0x21, 0x22      # slam_jpeg_info's sampling
 JPEG_EOF, JPEG_BAD_CODE, JPEG_RUN, JPEG_RESTART = 1, 2, 4, 8       # entropy fault bits of a decode's status
 JPEG_ENC_OVERFLOW, JPEG_ENC_CATEGORY = 1, 2                        # status bits of an encode
+VOC_SIFT, VOC_ORB = 0, 1                                           # slam_voc_*'s descriptor kind
 RENDER_POINT, RENDER_LINE, RENDER_FACE = 0, 1, 2                   # the kind in a rendered id (kind << 30 | index)
 RENDER_AUTO, RENDER_THREAD, RENDER_WAVE, RENDER_WAVE_FULL_LIST = 0, 1, 2, 3   # slam_render_views_dev's raster_mode
 SIFT_KERNEL_AUTO, SIFT_KERNEL_BAND,SIFT_KERNEL_TAB, SIFT_KERNEL_GENERAL, SIFT_KERNEL_COLS, SIFT_KERNEL_COLW = 0, 1, 2, 3, 4, 5
@@ -216,6 +217,19 @@ SIGNATURES = {
     "slam_mvs_fuse": (_I, [_P, _P, _I, _I, _SZ, _I, _I, _P, _P, _P, _P, _P, _P, _P, _D, _I, _I, _I, _P, _P, _I, _P]),
     "slam_mvs_last_timing": (_I, [_P, _P]),
     "slam_mvs_depth_host": (_I, [_P, _P, _I, _I, _I, _SZ, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "slam_voc_assign_dev": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P]),
+    "slam_voc_train_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "slam_bow_vectors_dev": (_I, [_P, _P, _P, _P, _I, _P, _I, _P, _P]),
+    "slam_bow_score_dev": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _P]),
+    "slam_bow_topk_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "slam_voc_assign": (_I, [_P, _P, _I, _P, _I, _I, _P, _P]),
+    "slam_voc_train": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "slam_bow_vectors": (_I, [_P, _P, _P, _I, _P, _I, _P, _P]),
+    "slam_bow_query": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "slam_voc_assign_host": (_I, [_P, _I, _P, _I, _I, _P, _P]),
+    "slam_voc_train_host": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "slam_bow_vectors_host": (_I, [_P, _P, _I, _P, _I, _P, _P]),
+    "slam_bow_score_host": (_I, [_P, _P, _I, _P, _P, _I, _I, _P]),
 }
 
 _lib = None

@@ -1477,7 +1477,7 @@ def define_camera_position(old_deque, last_id, fd):
 
 
 def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK=None, undistort="frames",
-              criteria=(50, 0.01), max_residual=0.01, tracker=None, klt=None, lens_model=None, dense=None):
+              criteria=(50, 0.01), max_residual=0.01, tracker=None, klt=None, lens_model=None, dense=None, loops=None):
     """src/main.cpp:71-107 slamMain: mainCycle restarts from the last pose until
     the sequence ends, then points.txt / colors.txt.  K (3x3 float64) is
     updated in place by BA, as the reference's calibrationMatrix is.  dist: the
@@ -1520,6 +1520,16 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
     gd.densePoints / gd.denseColors and, with out_dir, to dense_points.txt /
     dense_colors.txt in rawOutput's format.  The four result files are unchanged.
     A frame count that differs from the pose count raises.
+
+    loops (opt-in; a place.LoopParams, None keeps, computes and writes nothing): the
+    good frames are kept as for dense (both may be set), and after the last cycle
+    place.find_loops describes each of them (ops.fast + ops.describe with the run's
+    matcher), trains a vocabulary on them or loads loops.vocabulary, builds the
+    database, runs detect_loops and verifies every candidate (verify_loop), keeping
+    those with at least loops.min_inliers.  The result goes to gd.loops as (i, j,
+    score, n_matches, n_inliers, R, t) over the kept frames' indices and, with
+    out_dir, to loops.txt: one row `i j score n_matches n_inliers R(9) t(3)` per loop
+    in rawOutput's format.  The four result files are unchanged.
     Returns (GlobalData, Logs)."""
     if undistort not in ("frames", "points"):
         raise ValueError('undistort: "frames" or "points"')
@@ -1541,7 +1551,7 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
     if tracker is not None:
         cond.tracker = klt or KltParams()
     logs = Logs(out_dir if out_dir is not None else None)
-    if dense is not None:
+    if dense is not None or loops is not None:
         logs.frames = []
     gd = GlobalData()
     old, last_id = [], -1
@@ -1580,4 +1590,14 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
             with open(os.path.join(logs.out_dir, "dense_colors.txt"), "w") as f:
                 if len(gd.denseColors):
                     raw_output(gd.denseColors, f)
+    if loops is not None:
+        from .place import find_loops
+        if any(f is None for f in logs.frames):
+            raise RuntimeError("loops: a logged pose without its good frame")
+        # operations without a device context (a CPU implementation of ops) get the host twins
+        gd.loops = find_loops(logs.frames, K, cond, ops, loops, ctx=getattr(ops, "ctx", None), host=not hasattr(ops, "ctx"))
+        if logs.out_dir:
+            with open(os.path.join(logs.out_dir, "loops.txt"), "w") as f:
+                for i, j, sc, n, inl, R, t in gd.loops:
+                    raw_output(np.concatenate([[i, j, sc, n, inl], np.ravel(R), np.ravel(t)]), f)
     return gd, logs
