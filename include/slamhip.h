@@ -1255,6 +1255,79 @@ int slam_bow_vectors_host(const int32_t* word, const int32_t* offsets, int m, co
 int slam_bow_score_host(const uint32_t* q, const uint64_t* qtotal, int nq, const uint32_t* db, const uint64_t* dbtotal,
                         int m, int K, double* scores);
 
+/* ---- loop closing: the Sim(3) constraint of a loop and the map correction (loop.hip) ----
+ * Only + - * / and sqrt in f64, nothing contracted, every sum in the order that
+ * tests/loop_ref.py states, so device, host twin and reference agree bit for bit.
+ * A similarity is 8 doubles S = (sigma, qw, qx, qy, qz, tx, ty, tz) with a unit
+ * quaternion: x' = sigma R(q) x + t.  Every call is synchronous. */
+enum { SLAM_SIM3_OK = 0, SLAM_SIM3_NO_MODEL = 1, SLAM_SIM3_TOO_FEW = 2, SLAM_SIM3_CHOLESKY = 3 };
+/* The similarity between the two copies of the map at each of L loops, by RANSAC.
+ * Loop l owns the pairs [offsets[l], offsets[l + 1]) of d_a / d_b (n x 3 f64, device;
+ * offsets: host, L + 1 ascending values from >= 0) that should satisfy b = s R a + t;
+ * centres (host, L x 6) holds the camera centre that saw a, then the one that saw b.
+ * H hypotheses per loop (1..65536) come from three distinct pairs each, drawn on the
+ * host by the counter-based generator of loop_ref.py from `seed`; a hypothesis whose
+ * triangle is degenerate scores 0.  A pair is an inlier of (s, R, t) iff e^2 = |b - (s R
+ * a + t)|^2 <= tau^2 |b - c_b|^2 and e^2 <= tau^2 s^2 |a - c_a|^2 (an angle of about tau
+ * seen from either camera).  The most inliers win, ties to the lowest hypothesis; the
+ * winner is refined on its inliers by 4 Gauss-Newton steps (7 x 7 normal equations
+ * summed in the stated order, solved by Cholesky).  Outputs per loop: d_sim (8 f64),
+ * d_mask (one byte per pair, at the pair's index), d_count (the winner's inliers),
+ * d_status: SLAM_SIM3_OK; SLAM_SIM3_TOO_FEW (fewer than 3 pairs) and
+ * SLAM_SIM3_NO_MODEL (no hypothesis with 3 inliers) give the identity, a zero mask and
+ * count 0; SLAM_SIM3_CHOLESKY keeps the similarity reached before the failed step. */
+int slam_sim3_ransac_dev(slam_ctx* ctx, void* stream, const double* d_a, const double* d_b, const int32_t* offsets,
+                         int L, const double* centres, int H, double tau, uint64_t seed, double* d_sim,
+                         uint8_t* d_mask, int32_t* d_count, int32_t* d_status);
+/* The same on host buffers (staged through the context's workspace). */
+int slam_sim3_ransac(slam_ctx* ctx, const double* a, const double* b, const int32_t* offsets, int L,
+                     const double* centres, int H, double tau, uint64_t seed, double* sim, uint8_t* mask,
+                     int32_t* count, int32_t* status);
+/* Moves n map points (n x 3 f64, device) after their anchor nodes changed from
+ * nodes[anchor] to nodes_new[anchor] (host, m x 8 each): X' = S'^-1 (S (X)).  anchor
+ * (device, int32) -1, or outside [0, m), keeps the point; a node whose 8 values did not
+ * change returns its points' bits.  A node with sigma <= 0 or a zero quaternion is
+ * SLAM_E_INVALID_ARG. */
+int slam_sim3_apply_points_dev(slam_ctx* ctx, void* stream, const double* d_points, const int32_t* d_anchor, int n,
+                               const double* nodes, const double* nodes_new, int m, double* d_out);
+/* The same on host buffers; an anchor outside [-1, m) is SLAM_E_INVALID_ARG. */
+int slam_sim3_apply_points(slam_ctx* ctx, const double* points, const int32_t* anchor, int n, const double* nodes,
+                           const double* nodes_new, int m, double* out);
+/* Pose-graph optimisation over Sim(3).  d_nodes (device, n x 8, in and out): the
+ * keyframes' similarities, node 0 stays fixed.  Edge e joins nodes edges[2 e] = i and
+ * edges[2 e + 1] = j (host) with the measurement meas[e] (host, 8 f64, Z ~ S_i o
+ * S_j^-1) and weight[e] >= 0; its residual is sqrt(w) (sigma_E - 1, 2 sign(qw) vec(q_E),
+ * t_E / ell) of E = Z^-1 o S_i o S_j^-1, with analytic Jacobians in the local steps
+ * sigma (1 + ds), q (x) (1, dr / 2), t + dt.  Levenberg-Marquardt: lambda starts at
+ * lambda0 and multiplies the diagonal; a step that lowers the cost is accepted and
+ * lambda /= 10, otherwise the nodes are restored and lambda *= 10; it ends after max_lm
+ * steps, at cost 0, or after an accepted step with (cost - new) / cost < cost_tol.  Each
+ * step is solved by conjugate gradients on the normal equations, preconditioned by the
+ * Cholesky factors of the damped 7 x 7 diagonal blocks, until r.z <= pcg_tol (r.z)_0 or
+ * max_pcg iterations; the loop stays on the stream and the host reads its stop flag
+ * every 8 iterations.  Sums run in the orders of tests/loop_ref.py.  cost (host, 2):
+ * initial and final sum of squares; iters (host, 3): LM steps, accepted steps, PCG
+ * iterations in total.  SLAM_E_INVALID_ARG: an edge with i == j or an index outside
+ * [0, n), a node or measurement with sigma <= 0 or a zero quaternion, ell <= 0, a
+ * negative weight, cap or tolerance, a node that no edge reaches. */
+int slam_pgo_sim3_dev(slam_ctx* ctx, void* stream, double* d_nodes, int n, const int32_t* edges, const double* meas,
+                      const double* weight, int E, double ell, double lambda0, int max_lm, int max_pcg, double pcg_tol,
+                      double cost_tol, double* cost, int32_t* iters);
+/* The same with the nodes in host memory. */
+int slam_pgo_sim3(slam_ctx* ctx, double* nodes, int n, const int32_t* edges, const double* meas, const double* weight,
+                  int E, double ell, double lambda0, int max_lm, int max_pcg, double pcg_tol, double cost_tol,
+                  double* cost, int32_t* iters);
+/* The host twins: no context, no device, the same arithmetic (csrc/loop_math.h), the
+ * same results bit for bit. */
+int slam_pgo_sim3_host(double* nodes, int n, const int32_t* edges, const double* meas, const double* weight, int E,
+                       double ell, double lambda0, int max_lm, int max_pcg, double pcg_tol, double cost_tol, double* cost,
+                       int32_t* iters);
+int slam_sim3_ransac_host(const double* a, const double* b, const int32_t* offsets, int L, const double* centres,
+                          int H, double tau, uint64_t seed, double* sim, uint8_t* mask, int32_t* count,
+                          int32_t* status);
+int slam_sim3_apply_points_host(const double* points, const int32_t* anchor, int n, const double* nodes,
+                                const double* nodes_new, int m, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,661 @@
+// Loop closing: the Sim(3) constraint of each verified loop by a batched RANSAC, and the
+// correction of the map points, gfx950.
+//
+// The contract is tests/loop_ref.py; the arithmetic shared with the host twin
+// (loop_host.cpp) is loop_math.h: + - * / and sqrt in f64, nothing contracted, every
+// sum in a stated order, so every result equals the reference bit for bit.
+//
+//   sim3_hyp     one thread per (loop, hypothesis): the similarity of the sampled triangle
+//                pair (Gram-Schmidt frames), all zero when a triangle is degenerate.
+//   sim3_score   grid = (64-hypothesis tiles, loops), one wave per workgroup: a lane keeps
+//                one hypothesis in registers, the loop's pairs stream once through LDS in
+//                64-pair chunks (a, b and the two squared camera distances), every lane
+//                reads a pair as an LDS broadcast.  Integer counts, no atomics.
+//   sim3_refit   one wave per loop: the winner (most inliers, then the lowest hypothesis),
+//                its inlier mask, then kSim3RefitSteps Gauss-Newton steps.  The 35 sums of
+//                a step: lane l adds the pairs l, l + 64, ... in ascending order, then the
+//                lanes fold as a binary tree in LDS (+32, +16, ... +1); every lane solves
+//                the same 7 x 7 system by Cholesky.
+//   sim3_apply_points  one thread per map point: X' = S'^-1 (S (X)) of its anchor node.
+#include <algorithm>
+#include <utility>
+
+#include <vector>
+
+#include "loop_math.h"
+#include "slamhip_internal.h"
+
+namespace slamhip {
+
+namespace {
+
+__global__ __launch_bounds__(256) void sim3_hyp(const double* a, const double* b, const int32_t* offsets, int L, int H,
+                                                const int32_t* samples, double* hyp)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)L * H) return;
+    const int l = (int)(i / H);
+    const int lo = offsets[l], n = offsets[l + 1] - lo;
+    double S[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int s0 = samples[3 * i], s1 = samples[3 * i + 1], s2 = samples[3 * i + 2];
+    if (n >= 3 && (unsigned)s0 < (unsigned)n && (unsigned)s1 < (unsigned)n && (unsigned)s2 < (unsigned)n) {
+        const double* pa = a + 3 * (size_t)lo;
+        const double* pb = b + 3 * (size_t)lo;
+        double p[6][3];
+        for (int k = 0; k < 3; k++) {
+            p[0][k] = pa[3 * (size_t)s0 + k];
+            p[1][k] = pa[3 * (size_t)s1 + k];
+            p[2][k] = pa[3 * (size_t)s2 + k];
+            p[3][k] = pb[3 * (size_t)s0 + k];
+            p[4][k] = pb[3 * (size_t)s1 + k];
+            p[5][k] = pb[3 * (size_t)s2 + k];
+        }
+        sim3_hypothesis(p[0], p[1], p[2], p[3], p[4], p[5], S);
+    }
+    for (int k = 0; k < 8; k++) hyp[8 * i + k] = S[k];
+}
+
+constexpr int kScoreTile = 64;      // hypotheses per workgroup = pairs per LDS chunk
+
+__global__ __launch_bounds__(kScoreTile) void sim3_score(const double* a, const double* b, const int32_t* offsets,
+                                                         const double* centres, int H, double tau2, const double* hyp,
+                                                         int32_t* counts)
+{
+    __shared__ double pr[kScoreTile][8];        // a (3), b (3), |a - ci|^2, |b - cj|^2
+    const int l = blockIdx.y, lane = threadIdx.x;
+    const int h = blockIdx.x * kScoreTile + lane;
+    const int lo = offsets[l], n = offsets[l + 1] - lo;
+    double ci[3], cj[3];
+    for (int k = 0; k < 3; k++) {
+        ci[k] = centres[6 * (size_t)l + k];
+        cj[k] = centres[6 * (size_t)l + 3 + k];
+    }
+    double S[8] = {0, 0, 0, 0, 0, 0, 0, 0}, R[9];
+    if (h < H)
+        for (int k = 0; k < 8; k++) S[k] = hyp[8 * ((size_t)l * H + h) + k];
+    const bool live = h < H && S[0] > 0.0;
+    const double q1[4] = {1.0, 0.0, 0.0, 0.0};
+    quat_matrix(live ? S + 1 : q1, R);
+    int cnt = 0;
+    for (int base = 0; base < n; base += kScoreTile) {
+        const int k = base + lane;
+        if (k < n) {
+            double pa[3], pb[3];
+            for (int j = 0; j < 3; j++) {
+                pa[j] = a[3 * ((size_t)lo + k) + j];
+                pb[j] = b[3 * ((size_t)lo + k) + j];
+                pr[lane][j] = pa[j];
+                pr[lane][3 + j] = pb[j];
+            }
+            pr[lane][6] = dist2(pa, ci);
+            pr[lane][7] = dist2(pb, cj);
+        }
+        __syncthreads();
+        const int m = min(kScoreTile, n - base);
+        if (live)
+            for (int r = 0; r < m; r++) cnt += sim3_inlier(S[0], R, S + 5, &pr[r][0], &pr[r][3], pr[r][6], pr[r][7], tau2) ? 1 : 0;
+        __syncthreads();
+    }
+    if (h < H) counts[(size_t)l * H + h] = cnt;
+}
+
+__global__ __launch_bounds__(kSim3Lanes) void sim3_refit(const double* a, const double* b, const int32_t* offsets,
+                                                         const double* centres, int H, double tau2, const double* hyp,
+                                                         const int32_t* counts, double* sim, uint8_t* mask, int32_t* count,
+                                                         int32_t* status)
+{
+    __shared__ double part[kSim3Lanes][kSim3Terms];
+    const int l = blockIdx.x, lane = threadIdx.x;
+    const int lo = offsets[l], n = offsets[l + 1] - lo;
+    const double* pa = a + 3 * (size_t)lo;
+    const double* pb = b + 3 * (size_t)lo;
+    uint8_t* mk = mask + lo;
+
+    // the winner: most inliers, then the lowest hypothesis
+    int bc = -1, bh = 0x7fffffff;
+    if (n >= 3)
+        for (int h = lane; h < H; h += kSim3Lanes) {
+            const int c = counts[(size_t)l * H + h];
+            if (c > bc) {       // ascending h per lane: strict keeps the lower
+                bc = c;
+                bh = h;
+            }
+        }
+    for (int off = 32; off >= 1; off >>= 1) {
+        const int oc = __shfl_xor(bc, off, 64), oh = __shfl_xor(bh, off, 64);
+        if (oc > bc || (oc == bc && oh < bh)) {
+            bc = oc;
+            bh = oh;
+        }
+    }
+    double S[8] = {1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (n < 3 || bc < 3) {
+        for (int k = lane; k < n; k += kSim3Lanes) mk[k] = 0;
+        if (lane == 0) {
+            for (int k = 0; k < 8; k++) sim[8 * (size_t)l + k] = S[k];
+            count[l] = 0;
+            status[l] = n < 3 ? kSim3TooFew : kSim3NoModel;
+        }
+        return;
+    }
+    for (int k = 0; k < 8; k++) S[k] = hyp[8 * ((size_t)l * H + bh) + k];
+    double ci[3], cj[3], R[9];
+    for (int k = 0; k < 3; k++) {
+        ci[k] = centres[6 * (size_t)l + k];
+        cj[k] = centres[6 * (size_t)l + 3 + k];
+    }
+    quat_matrix(S + 1, R);
+    for (int k = lane; k < n; k += kSim3Lanes) {
+        double xa[3], xb[3];
+        for (int j = 0; j < 3; j++) {
+            xa[j] = pa[3 * (size_t)k + j];
+            xb[j] = pb[3 * (size_t)k + j];
+        }
+        mk[k] = sim3_inlier(S[0], R, S + 5, xa, xb, dist2(xa, ci), dist2(xb, cj), tau2) ? 1 : 0;
+    }
+    // a lane reads back only the mask bytes it wrote itself (k = lane mod 64)
+    int st = kSim3Ok;
+    for (int it = 0; it < kSim3RefitSteps; it++) {
+        double acc[kSim3Terms];
+        for (int j = 0; j < kSim3Terms; j++) acc[j] = 0.0;
+        quat_matrix(S + 1, R);
+        for (int k = lane; k < n; k += kSim3Lanes) {
+            double xa[3], xb[3], term[kSim3Terms];
+            for (int j = 0; j < 3; j++) {
+                xa[j] = pa[3 * (size_t)k + j];
+                xb[j] = pb[3 * (size_t)k + j];
+            }
+            sim3_terms(S[0], R, S + 5, xa, xb, term);
+            const bool in = mk[k] != 0;
+            for (int j = 0; j < kSim3Terms; j++) acc[j] = acc[j] + (in ? term[j] : 0.0);
+        }
+        __syncthreads();        // the previous step's reads of part[0] are done
+        for (int j = 0; j < kSim3Terms; j++) part[lane][j] = acc[j];
+        __syncthreads();
+        for (int off = kSim3Lanes / 2; off >= 1; off >>= 1) {
+            if (lane < off)
+                for (int j = 0; j < kSim3Terms; j++) part[lane][j] = part[lane][j] + part[lane + off][j];
+            __syncthreads();
+        }
+        double sum[kSim3Terms], d[7];
+        for (int j = 0; j < kSim3Terms; j++) sum[j] = part[0][j];
+        if (!chol7_solve(sum, sum + 28, d)) {       // uniform: every lane has the same sums
+            st = kSim3Cholesky;
+            break;
+        }
+        sim3_step(S, d);
+    }
+    if (lane == 0) {
+        for (int k = 0; k < 8; k++) sim[8 * (size_t)l + k] = S[k];
+        count[l] = bc;
+        status[l] = st;
+    }
+}
+
+__global__ __launch_bounds__(256) void sim3_apply_points(const double* pts, const int32_t* anchor, int n, const double* nodes,
+                                                         const double* nodes_new, int m, double* out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int an = anchor[i];
+    double X[3], Y[3];
+    for (int k = 0; k < 3; k++) X[k] = pts[3 * (size_t)i + k];
+    if ((unsigned)an < (unsigned)m) {
+        double S[8], Sn[8];
+        for (int k = 0; k < 8; k++) {
+            S[k] = nodes[8 * (size_t)an + k];
+            Sn[k] = nodes_new[8 * (size_t)an + k];
+        }
+        sim3_move_point(S, Sn, X, Y);
+    } else {
+        for (int k = 0; k < 3; k++) Y[k] = X[k];
+    }
+    for (int k = 0; k < 3; k++) out[3 * (size_t)i + k] = Y[k];
+}
+
+// ---- the pose graph over Sim(3): LM with a block-Jacobi PCG whose loop stays on the stream ----
+//   pgo_linearize  one thread per edge: residual, both Jacobians, |r|^2
+//   pgo_assemble   one thread per (node, row): the row of H_aa and g_a over the node's incident list in order
+//   pgo_damp       one thread per node: Hd = H + lambda diag(H) and its Cholesky factor
+//   pgo_edge_mul   one thread per (edge, side): u = J p
+//   pgo_apply      one thread per (node, row): Hd_aa p_a + sum J_a^T u_b over the same list
+//   pgo_reduce     one workgroup of 1024: the 1024 strided partial sums, the binary tree in LDS, and the
+//                  scalar work of its step (cost; rz0 and the start flag; alpha; beta, the count and the
+//                  stop flag).  Once the stop flag is set every kernel of the loop returns at once.
+struct PgoSc {
+    double rz, rz0, alpha, beta, cost, tol;
+    int done, iters;
+};
+
+__global__ __launch_bounds__(64) void pgo_linearize(const double* S, const int32_t* edges, const double* zinv,
+                                                    const double* sw, int E, double ell, double* r, double* J, double* c)
+{
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= E) return;
+    const int i = edges[2 * (size_t)e], j = edges[2 * (size_t)e + 1];
+    double Si[8], Sj[8], A[8], rr[7], Ji[49], Jj[49];
+    for (int k = 0; k < 8; k++) {
+        Si[k] = S[8 * (size_t)i + k];
+        Sj[k] = S[8 * (size_t)j + k];
+        A[k] = zinv[8 * (size_t)e + k];
+    }
+    pgo_edge(Si, Sj, A, sw[e], ell, i == 0, j == 0, rr, Ji, Jj);
+    for (int k = 0; k < 7; k++) r[7 * (size_t)e + k] = rr[k];
+    for (int k = 0; k < 49; k++) {
+        J[98 * (size_t)e + k] = Ji[k];
+        J[98 * (size_t)e + 49 + k] = Jj[k];
+    }
+    c[e] = pgo_edge_cost(rr);
+}
+
+__global__ __launch_bounds__(kPgoLanes) void pgo_reduce(const double* a, const double* b, size_t n, PgoSc* sc, int mode)
+{
+    __shared__ double part[kPgoLanes];
+    if (mode >= 2 && sc->done) return;      // uniform
+    const int t = threadIdx.x;
+    double acc = 0.0;
+    for (size_t i = t; i < n; i += kPgoLanes) acc = acc + (b ? a[i] * b[i] : a[i]);
+    part[t] = acc;
+    __syncthreads();
+    for (int off = kPgoLanes / 2; off >= 1; off >>= 1) {
+        if (t < off) part[t] = part[t] + part[t + off];
+        __syncthreads();
+    }
+    if (t != 0) return;
+    const double sum = part[0];
+    if (mode == 0) {
+        sc->cost = sum;
+    } else if (mode == 1) {
+        sc->rz = sum;
+        sc->rz0 = sum;
+        sc->done = sum > 0.0 ? 0 : 1;
+        sc->iters = 0;
+    } else if (mode == 2) {
+        if (!(sum > 0.0))
+            sc->done = 1;
+        else
+            sc->alpha = sc->rz / sum;
+    } else {
+        sc->iters = sc->iters + 1;
+        if (sum <= sc->tol * sc->rz0)
+            sc->done = 1;
+        else
+            sc->beta = sum / sc->rz;
+        sc->rz = sum;
+    }
+}
+
+__global__ __launch_bounds__(256) void pgo_assemble(const double* r, const double* J, const int32_t* start, const int32_t* ent,
+                                                    int n, double* H, double* g)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 7 * n) return;
+    const int a = i / 7, row = i - 7 * a;
+    double h[7] = {0, 0, 0, 0, 0, 0, 0}, gs = 0.0;
+    for (int q = start[a]; q < start[a + 1]; q++) {
+        const int en = ent[q];
+        double hb[7], gb;
+        pgo_block_row(J + 49 * (size_t)en, r + 7 * (size_t)(en >> 1), row, hb, &gb);
+        for (int k = 0; k < 7; k++) h[k] = h[k] + hb[k];
+        gs = gs - gb;
+    }
+    for (int k = 0; k < 7; k++) H[49 * (size_t)a + 7 * row + k] = h[k];
+    g[i] = gs;
+}
+
+__global__ __launch_bounds__(64) void pgo_damp(const double* H, double lambda, int n, double* Hd, double* Lm)
+{
+    const int a = blockIdx.x * 64 + threadIdx.x;
+    if (a >= n) return;
+    double h[49], hd[49], l[49];
+    for (int k = 0; k < 49; k++) h[k] = H[49 * (size_t)a + k];
+    pgo_damp_block(h, lambda, a == 0, hd, l);
+    for (int k = 0; k < 49; k++) {
+        Hd[49 * (size_t)a + k] = hd[k];
+        Lm[49 * (size_t)a + k] = l[k];
+    }
+}
+
+__global__ __launch_bounds__(64) void pgo_pcg_init(const double* g, const double* Lm, int n, double* x, double* r, double* z,
+                                                   double* p)
+{
+    const int a = blockIdx.x * 64 + threadIdx.x;
+    if (a >= n) return;
+    double rr[7], zz[7];
+    for (int k = 0; k < 7; k++) rr[k] = g[7 * (size_t)a + k];
+    pgo_block_solve(Lm + 49 * (size_t)a, rr, zz);
+    for (int k = 0; k < 7; k++) {
+        x[7 * (size_t)a + k] = 0.0;
+        r[7 * (size_t)a + k] = rr[k];
+        z[7 * (size_t)a + k] = zz[k];
+        p[7 * (size_t)a + k] = zz[k];
+    }
+}
+
+__global__ __launch_bounds__(256) void pgo_edge_mul(const double* J, const int32_t* edges, int E2, const double* p, double* u,
+                                                    const PgoSc* sc)
+{
+    if (sc->done) return;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= E2) return;
+    double pp[7], uu[7];
+    const int node = edges[q];
+    for (int k = 0; k < 7; k++) pp[k] = p[7 * (size_t)node + k];
+    pgo_jp(J + 49 * (size_t)q, pp, uu);
+    for (int k = 0; k < 7; k++) u[7 * (size_t)q + k] = uu[k];
+}
+
+__global__ __launch_bounds__(256) void pgo_apply(const double* J, const double* Hd, const int32_t* start, const int32_t* ent, int n,
+                                                 const double* p, const double* u, double* Ap, const PgoSc* sc)
+{
+    if (sc->done) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 7 * n) return;
+    const int a = i / 7, row = i - 7 * a;
+    const double* hd = Hd + 49 * (size_t)a + 7 * row;
+    const double* pa = p + 7 * (size_t)a;
+    double y = hd[0] * pa[0];
+    for (int k = 1; k < 7; k++) y = y + hd[k] * pa[k];
+    for (int q = start[a]; q < start[a + 1]; q++) {
+        const int en = ent[q];
+        y = y + pgo_jtu(J + 49 * (size_t)en, u + 7 * (size_t)(en ^ 1), row);
+    }
+    Ap[i] = y;
+}
+
+__global__ __launch_bounds__(64) void pgo_update(const double* Lm, int n, const double* p, const double* Ap, double* x, double* r,
+                                                 double* z, const PgoSc* sc)
+{
+    if (sc->done) return;
+    const int a = blockIdx.x * 64 + threadIdx.x;
+    if (a >= n) return;
+    const double alpha = sc->alpha;
+    double rr[7], zz[7];
+    for (int k = 0; k < 7; k++) {
+        const size_t i = 7 * (size_t)a + k;
+        x[i] = x[i] + alpha * p[i];
+        rr[k] = r[i] - alpha * Ap[i];
+        r[i] = rr[k];
+    }
+    pgo_block_solve(Lm + 49 * (size_t)a, rr, zz);
+    for (int k = 0; k < 7; k++) z[7 * (size_t)a + k] = zz[k];
+}
+
+__global__ __launch_bounds__(256) void pgo_pupdate(int N, const double* z, double* p, const PgoSc* sc)
+{
+    if (sc->done) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    p[i] = z[i] + sc->beta * p[i];
+}
+
+__global__ __launch_bounds__(256) void pgo_step(const double* S, const double* x, int n, double* St)
+{
+    const int a = blockIdx.x * 256 + threadIdx.x;
+    if (a >= n) return;
+    double s[8], d[7];
+    for (int k = 0; k < 8; k++) s[k] = S[8 * (size_t)a + k];
+    for (int k = 0; k < 7; k++) d[k] = x[7 * (size_t)a + k];
+    if (a > 0) sim3_step(s, d);
+    for (int k = 0; k < 8; k++) St[8 * (size_t)a + k] = s[k];
+}
+
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+}  // namespace
+
+}  // namespace slamhip
+
+using namespace slamhip;
+
+extern "C" int slam_sim3_ransac_dev(slam_ctx* c, void* stream, const double* d_a, const double* d_b, const int32_t* offsets,
+                                    int L, const double* centres, int H, double tau, uint64_t seed, double* d_sim,
+                                    uint8_t* d_mask, int32_t* d_count, int32_t* d_status)
+{
+    if (!c) return SLAM_E_INVALID_ARG;
+    if (loop_check_ransac(offsets, L, centres, H, tau))
+        return set_err(c, SLAM_E_INVALID_ARG, "sim3 ransac: 0 <= L <= 65535, 1 <= H <= 65536, tau > 0, offsets ascending "
+                                              "from >= 0 with at most 2^24 pairs per loop");
+    if (L == 0) return SLAM_OK;
+    const int np = offsets[L] - offsets[0];
+    if (!d_sim || !d_count || !d_status || (np > 0 && (!d_a || !d_b || !d_mask)))
+        return set_err(c, SLAM_E_INVALID_ARG, "sim3 ransac: null argument");
+    SLAM_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    const size_t LH = (size_t)L * H;
+    std::vector<int32_t> samples(3 * LH);
+    loop_draw_samples(offsets, L, H, seed, samples.data());
+    // hypotheses and centres (f64) first, then the samples, the counts and the offsets
+    const size_t o_cen = 8 * 8 * LH, o_smp = o_cen + 8 * 6 * (size_t)L, o_cnt = o_smp + 4 * 3 * LH, o_off = o_cnt + 4 * LH;
+    SLAM_HIP(c, c->loop_ws.ensure(o_off + 4 * ((size_t)L + 1)));
+    uint8_t* w = c->loop_ws.as<uint8_t>();
+    double* hyp = reinterpret_cast<double*>(w);
+    double* cen = reinterpret_cast<double*>(w + o_cen);
+    int32_t* smp = reinterpret_cast<int32_t*>(w + o_smp);
+    int32_t* cnt = reinterpret_cast<int32_t*>(w + o_cnt);
+    int32_t* off = reinterpret_cast<int32_t*>(w + o_off);
+    SLAM_HIP(c, hipMemcpyAsync(cen, centres, 8 * 6 * (size_t)L, hipMemcpyHostToDevice, s));
+    SLAM_HIP(c, hipMemcpyAsync(smp, samples.data(), 4 * 3 * LH, hipMemcpyHostToDevice, s));
+    SLAM_HIP(c, hipMemcpyAsync(off, offsets, 4 * ((size_t)L + 1), hipMemcpyHostToDevice, s));
+    const double tau2 = tau * tau;
+    hipLaunchKernelGGL(sim3_hyp, dim3((unsigned)((LH + 255) / 256)), dim3(256), 0, s, d_a, d_b, off, L, H, smp, hyp);
+    hipLaunchKernelGGL(sim3_score, dim3((H + kScoreTile - 1) / kScoreTile, L), dim3(kScoreTile), 0, s, d_a, d_b, off, cen, H,
+                       tau2, hyp, cnt);
+    hipLaunchKernelGGL(sim3_refit, dim3(L), dim3(kSim3Lanes), 0, s, d_a, d_b, off, cen, H, tau2, hyp, cnt, d_sim, d_mask,
+                       d_count, d_status);
+    SLAM_HIP(c, hipGetLastError());
+    return stream_sync(c, s);       // the sample table lives until here
+}
+
+extern "C" int slam_sim3_apply_points_dev(slam_ctx* c, void* stream, const double* d_points, const int32_t* d_anchor, int n,
+                                          const double* nodes, const double* nodes_new, int m, double* d_out)
+{
+    if (!c) return SLAM_E_INVALID_ARG;
+    if (n < 0 || loop_check_nodes(nodes, m) || loop_check_nodes(nodes_new, m))
+        return set_err(c, SLAM_E_INVALID_ARG, "sim3 apply points: n, m >= 0, every node with sigma > 0 and a non-zero quaternion");
+    if (n == 0) return SLAM_OK;
+    if (!d_points || !d_anchor || !d_out) return set_err(c, SLAM_E_INVALID_ARG, "sim3 apply points: null argument");
+    SLAM_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    const size_t nb = 8 * 8 * (size_t)m;
+    SLAM_HIP(c, c->loop_ws.ensure(2 * nb + 8));
+    double* dn = c->loop_ws.as<double>();
+    if (m > 0) {
+        SLAM_HIP(c, hipMemcpyAsync(dn, nodes, nb, hipMemcpyHostToDevice, s));
+        SLAM_HIP(c, hipMemcpyAsync(dn + 8 * (size_t)m, nodes_new, nb, hipMemcpyHostToDevice, s));
+    }
+    hipLaunchKernelGGL(sim3_apply_points, dim3((n + 255) / 256), dim3(256), 0, s, d_points, d_anchor, n, dn, dn + 8 * (size_t)m, m,
+                       d_out);
+    SLAM_HIP(c, hipGetLastError());
+    return stream_sync(c, s);
+}
+
+extern "C" int slam_pgo_sim3_dev(slam_ctx* c, void* stream, double* d_nodes, int n, const int32_t* edges, const double* meas,
+                                 const double* weight, int E, double ell, double lambda0, int max_lm, int max_pcg,
+                                 double pcg_tol, double cost_tol, double* cost, int32_t* iters)
+{
+    if (!c) return SLAM_E_INVALID_ARG;
+    if (n < 1 || n > kSim3MaxPairs || !d_nodes || !cost || !iters)
+        return set_err(c, SLAM_E_INVALID_ARG, "pgo sim3: null argument or no node");
+    SLAM_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    std::vector<double> h_nodes(8 * (size_t)n);
+    SLAM_HIP(c, hipMemcpyAsync(h_nodes.data(), d_nodes, 8 * 8 * (size_t)n, hipMemcpyDeviceToHost, s));
+    if (int rc = stream_sync(c, s)) return rc;
+    if (loop_check_pgo(h_nodes.data(), n, edges, meas, weight, E, ell, lambda0, max_lm, max_pcg, pcg_tol, cost_tol))
+        return set_err(c, SLAM_E_INVALID_ARG, "pgo sim3: every node and measurement with sigma > 0 and a non-zero quaternion, "
+                                              "edges i != j inside [0, n) that reach every node, weights >= 0, ell > 0, "
+                                              "lambda0, caps and tolerances >= 0");
+    std::vector<int32_t> start, ent;
+    pgo_build_csr(n, edges, E, start, ent);
+    std::vector<double> zs(9 * (size_t)E);
+    pgo_edge_constants(meas, weight, E, zs.data(), zs.data() + 8 * (size_t)E);
+    const size_t N = 7 * (size_t)n, nE = (size_t)E;
+    // f64: S, St, zinv + sw, two linearisations (r, J, c), H, g, Hd, L, x, r, z, p, Ap, u, the scalars; then the ints
+    const size_t lin = 7 * nE + 98 * nE + nE;
+    const size_t nd = 16 * (size_t)n + 9 * nE + 2 * lin + 3 * 49 * (size_t)n + 6 * N + 14 * nE + 8;
+    const size_t ni = 2 * nE + ((size_t)n + 1) + 2 * nE;
+    SLAM_HIP(c, c->loop_pgo.ensure(8 * nd + 4 * ni));
+    double* w = c->loop_pgo.as<double>();
+    double *S = w, *St = S + 8 * (size_t)n, *zinv = St + 8 * (size_t)n, *sw = zinv + 8 * nE, *linA = sw + nE, *linB = linA + lin;
+    double *H = linB + lin, *Hd = H + 49 * (size_t)n, *Lm = Hd + 49 * (size_t)n, *g = Lm + 49 * (size_t)n;
+    double *x = g + N, *r = x + N, *z = r + N, *p = z + N, *Ap = p + N, *u = Ap + N;
+    PgoSc* sc = reinterpret_cast<PgoSc*>(u + 14 * nE);
+    static_assert(sizeof(PgoSc) <= 8 * 8, "the scalars fit their slot");
+    int32_t* d_edges = reinterpret_cast<int32_t*>(w + nd);
+    int32_t *d_start = d_edges + 2 * nE, *d_ent = d_start + n + 1;
+    PgoSc* h_sc = static_cast<PgoSc*>(readback(c, sizeof(PgoSc)));
+    if (!h_sc) return set_err(c, SLAM_E_HIP, "pgo sim3: no pinned readback space");
+
+    SLAM_HIP(c, hipMemcpyAsync(S, d_nodes, 8 * 8 * (size_t)n, hipMemcpyDeviceToDevice, s));
+    if (E > 0) {
+        SLAM_HIP(c, hipMemcpyAsync(zinv, zs.data(), 8 * 9 * nE, hipMemcpyHostToDevice, s));
+        SLAM_HIP(c, hipMemcpyAsync(d_edges, edges, 4 * 2 * nE, hipMemcpyHostToDevice, s));
+        SLAM_HIP(c, hipMemcpyAsync(d_ent, ent.data(), 4 * 2 * nE, hipMemcpyHostToDevice, s));
+    }
+    SLAM_HIP(c, hipMemcpyAsync(d_start, start.data(), 4 * ((size_t)n + 1), hipMemcpyHostToDevice, s));
+    PgoSc init = {};
+    init.tol = pcg_tol;
+    SLAM_HIP(c, hipMemcpyAsync(sc, &init, sizeof(PgoSc), hipMemcpyHostToDevice, s));
+    if (int rc = stream_sync(c, s)) return rc;      // the host vectors and `init` are free from here
+
+    const unsigned gE = (unsigned)((E + 63) / 64), gN7 = (unsigned)((N + 255) / 256), gN = (unsigned)((n + 63) / 64);
+    auto linearize = [&](const double* nodes, double* L, double* out) -> int {
+        if (E > 0) hipLaunchKernelGGL(pgo_linearize, dim3(gE), dim3(64), 0, s, nodes, d_edges, zinv, sw, E, ell, L, L + 7 * nE, L + 105 * nE);
+        hipLaunchKernelGGL(pgo_reduce, dim3(1), dim3(kPgoLanes), 0, s, L + 105 * nE, (const double*)nullptr, nE, sc, 0);
+        SLAM_HIP(c, hipGetLastError());
+        SLAM_HIP(c, hipMemcpyAsync(h_sc, sc, sizeof(PgoSc), hipMemcpyDeviceToHost, s));
+        if (int rc = stream_sync(c, s, true)) return rc;
+        *out = h_sc->cost;
+        return SLAM_OK;
+    };
+    double c0 = 0.0;
+    if (int rc = linearize(S, linA, &c0)) return rc;
+    double cur = c0, lambda = lambda0;
+    int lm = 0, accepted = 0, pcg_total = 0;
+    while (lm < max_lm && cur > 0.0) {
+        const double *rA = linA, *JA = linA + 7 * nE;
+        hipLaunchKernelGGL(pgo_assemble, dim3(gN7), dim3(256), 0, s, rA, JA, d_start, d_ent, n, H, g);
+        hipLaunchKernelGGL(pgo_damp, dim3(gN), dim3(64), 0, s, H, lambda, n, Hd, Lm);
+        hipLaunchKernelGGL(pgo_pcg_init, dim3(gN), dim3(64), 0, s, g, Lm, n, x, r, z, p);
+        hipLaunchKernelGGL(pgo_reduce, dim3(1), dim3(kPgoLanes), 0, s, r, z, N, sc, 1);
+        SLAM_HIP(c, hipGetLastError());
+        int launched = 0;
+        for (;;) {
+            const int chunk = std::min(kPgoChunk, max_pcg - launched);
+            for (int k = 0; k < chunk; k++) {
+                if (E > 0) hipLaunchKernelGGL(pgo_edge_mul, dim3((unsigned)((2 * nE + 255) / 256)), dim3(256), 0, s, JA, d_edges, 2 * E, p, u, sc);
+                hipLaunchKernelGGL(pgo_apply, dim3(gN7), dim3(256), 0, s, JA, Hd, d_start, d_ent, n, p, u, Ap, sc);
+                hipLaunchKernelGGL(pgo_reduce, dim3(1), dim3(kPgoLanes), 0, s, p, Ap, N, sc, 2);
+                hipLaunchKernelGGL(pgo_update, dim3(gN), dim3(64), 0, s, Lm, n, p, Ap, x, r, z, sc);
+                hipLaunchKernelGGL(pgo_reduce, dim3(1), dim3(kPgoLanes), 0, s, r, z, N, sc, 3);
+                hipLaunchKernelGGL(pgo_pupdate, dim3(gN7), dim3(256), 0, s, (int)N, z, p, sc);
+            }
+            launched += chunk;
+            SLAM_HIP(c, hipGetLastError());
+            SLAM_HIP(c, hipMemcpyAsync(h_sc, sc, sizeof(PgoSc), hipMemcpyDeviceToHost, s));
+            if (int rc = stream_sync(c, s, true)) return rc;
+            if (h_sc->done || launched >= max_pcg) break;
+        }
+        pcg_total += h_sc->iters;
+        hipLaunchKernelGGL(pgo_step, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, S, x, n, St);
+        double ct = 0.0;
+        if (int rc = linearize(St, linB, &ct)) return rc;
+        lm++;
+        if (ct < cur) {
+            const double rel = (cur - ct) / cur;
+            std::swap(S, St);
+            std::swap(linA, linB);
+            cur = ct;
+            accepted++;
+            lambda = lambda / 10.0;
+            if (rel < cost_tol) break;
+        } else {
+            lambda = lambda * 10.0;
+        }
+    }
+    SLAM_HIP(c, hipMemcpyAsync(d_nodes, S, 8 * 8 * (size_t)n, hipMemcpyDeviceToDevice, s));
+    cost[0] = c0;
+    cost[1] = cur;
+    iters[0] = lm;
+    iters[1] = accepted;
+    iters[2] = pcg_total;
+    return stream_sync(c, s);
+}
+
+extern "C" int slam_pgo_sim3(slam_ctx* c, double* nodes, int n, const int32_t* edges, const double* meas, const double* weight,
+                             int E, double ell, double lambda0, int max_lm, int max_pcg, double pcg_tol, double cost_tol,
+                             double* cost, int32_t* iters)
+{
+    if (!c) return SLAM_E_INVALID_ARG;
+    if (loop_check_pgo(nodes, n, edges, meas, weight, E, ell, lambda0, max_lm, max_pcg, pcg_tol, cost_tol) || !cost || !iters)
+        return set_err(c, SLAM_E_INVALID_ARG, "pgo sim3: bad arguments");
+    SLAM_HIP(c, hipSetDevice(c->device));
+    SLAM_HIP(c, c->loop_in.ensure(8 * 8 * (size_t)n));
+    double* d = c->loop_in.as<double>();
+    SLAM_HIP(c, hipMemcpyAsync(d, nodes, 8 * 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    if (int rc = slam_pgo_sim3_dev(c, c->stream, d, n, edges, meas, weight, E, ell, lambda0, max_lm, max_pcg, pcg_tol, cost_tol,
+                                   cost, iters))
+        return rc;
+    SLAM_HIP(c, hipMemcpyAsync(nodes, d, 8 * 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    return stream_sync(c, c->stream);
+}
+
+// ---- host-buffer wrappers: stage, run the device entry points, copy back ----
+
+extern "C" int slam_sim3_ransac(slam_ctx* c, const double* a, const double* b, const int32_t* offsets, int L,
+                                const double* centres, int H, double tau, uint64_t seed, double* sim, uint8_t* mask,
+                                int32_t* count, int32_t* status)
+{
+    if (!c) return SLAM_E_INVALID_ARG;
+    if (loop_check_ransac(offsets, L, centres, H, tau)) return set_err(c, SLAM_E_INVALID_ARG, "sim3 ransac: bad arguments");
+    if (L == 0) return SLAM_OK;
+    const int32_t p0 = offsets[0], np = offsets[L] - offsets[0];
+    if (!sim || !count || !status || (np > 0 && (!a || !b || !mask))) return set_err(c, SLAM_E_INVALID_ARG, "sim3 ransac: null argument");
+    SLAM_HIP(c, hipSetDevice(c->device));
+    std::vector<int32_t> off((size_t)L + 1);
+    for (int i = 0; i <= L; i++) off[i] = offsets[i] - p0;
+    const size_t pb = 8 * 3 * (size_t)(np > 0 ? np : 1);
+    const size_t o_b = up256(pb), o_sim = o_b + up256(pb), o_cnt = o_sim + up256(8 * 8 * (size_t)L);
+    const size_t o_st = o_cnt + up256(4 * (size_t)L), o_mask = o_st + up256(4 * (size_t)L);
+    SLAM_HIP(c, c->loop_in.ensure(o_mask + (size_t)(np > 0 ? np : 1)));
+    uint8_t* d = c->loop_in.as<uint8_t>();
+    hipStream_t s = c->stream;
+    if (np > 0) {
+        SLAM_HIP(c, hipMemcpyAsync(d, a + 3 * (size_t)p0, 8 * 3 * (size_t)np, hipMemcpyHostToDevice, s));
+        SLAM_HIP(c, hipMemcpyAsync(d + o_b, b + 3 * (size_t)p0, 8 * 3 * (size_t)np, hipMemcpyHostToDevice, s));
+    }
+    if (int rc = slam_sim3_ransac_dev(c, s, reinterpret_cast<double*>(d), reinterpret_cast<double*>(d + o_b), off.data(), L, centres,
+                                      H, tau, seed, reinterpret_cast<double*>(d + o_sim), d + o_mask,
+                                      reinterpret_cast<int32_t*>(d + o_cnt), reinterpret_cast<int32_t*>(d + o_st)))
+        return rc;
+    SLAM_HIP(c, hipMemcpyAsync(sim, d + o_sim, 8 * 8 * (size_t)L, hipMemcpyDeviceToHost, s));
+    SLAM_HIP(c, hipMemcpyAsync(count, d + o_cnt, 4 * (size_t)L, hipMemcpyDeviceToHost, s));
+    SLAM_HIP(c, hipMemcpyAsync(status, d + o_st, 4 * (size_t)L, hipMemcpyDeviceToHost, s));
+    if (np > 0) SLAM_HIP(c, hipMemcpyAsync(mask + p0, d + o_mask, (size_t)np, hipMemcpyDeviceToHost, s));
+    return stream_sync(c, s);
+}
+
+extern "C" int slam_sim3_apply_points(slam_ctx* c, const double* points, const int32_t* anchor, int n, const double* nodes,
+                                      const double* nodes_new, int m, double* out)
+{
+    if (!c) return SLAM_E_INVALID_ARG;
+    if (n < 0 || loop_check_nodes(nodes, m) || loop_check_nodes(nodes_new, m))
+        return set_err(c, SLAM_E_INVALID_ARG, "sim3 apply points: bad arguments");
+    if (n == 0) return SLAM_OK;
+    if (!points || !anchor || !out) return set_err(c, SLAM_E_INVALID_ARG, "sim3 apply points: null argument");
+    for (int i = 0; i < n; i++)
+        if (anchor[i] < -1 || anchor[i] >= m) return set_err(c, SLAM_E_INVALID_ARG, "sim3 apply points: anchor outside [-1, m)");
+    SLAM_HIP(c, hipSetDevice(c->device));
+    const size_t pb = 8 * 3 * (size_t)n, o_out = up256(pb), o_an = o_out + up256(pb);
+    SLAM_HIP(c, c->loop_in.ensure(o_an + 4 * (size_t)n));
+    uint8_t* d = c->loop_in.as<uint8_t>();
+    hipStream_t s = c->stream;
+    SLAM_HIP(c, hipMemcpyAsync(d, points, pb, hipMemcpyHostToDevice, s));
+    SLAM_HIP(c, hipMemcpyAsync(d + o_an, anchor, 4 * (size_t)n, hipMemcpyHostToDevice, s));
+    if (int rc = slam_sim3_apply_points_dev(c, s, reinterpret_cast<double*>(d), reinterpret_cast<int32_t*>(d + o_an), n, nodes,
+                                            nodes_new, m, reinterpret_cast<double*>(d + o_out)))
+        return rc;
+    SLAM_HIP(c, hipMemcpyAsync(out, d + o_out, pb, hipMemcpyDeviceToHost, s));
+    return stream_sync(c, s);
+}

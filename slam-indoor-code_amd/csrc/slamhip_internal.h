@@ -348,6 +348,10 @@ struct slam_ctx {
     // words + distances + sorted order, its counts + starts + cursors + changed flag, the uploaded
     // offsets + weights, the staged buffers of the host-pointer calls
     slamhip::DevBuf place_part, place_norm, place_word, place_cnt, place_par, place_in;
+    // loop closing (loop.hip): the hypotheses + centres + sample table + counts + offsets of a RANSAC call (or
+    // the two node lists of a point correction), the staged buffers of the host-pointer calls
+    slamhip::DevBuf loop_ws, loop_in;
+    slamhip::DevBuf loop_pgo;             // slam_pgo_sim3_dev: nodes, linearisations, blocks, PCG vectors, scalars, lists
 
     bool prof_on = false;
     slamhip::ProfFamily prof[slamhip::kProfFamilies];
@@ -679,6 +683,18 @@ int place_check_train(const void* desc, int n, int K, int iters, int kind, const
 int place_check_vectors(const int32_t* offsets, int m, const int32_t* weights, int K);
 int place_check_score(int nq, int m, int K);
 int place_check_topk(int nq, int m, int first, int last, int k);
+// ---- loop closing (loop.hip, loop_host.cpp) ----
+// argument checks and the sample table shared by the device entry points and the host twins (loop_host.cpp)
+int loop_check_ransac(const int32_t* offsets, int L, const double* centres, int H, double tau);
+int loop_check_nodes(const double* nodes, int m);
+// samples: L x H x 3 indices into each loop's pairs (zeros for a loop with fewer than 3)
+void loop_draw_samples(const int32_t* offsets, int L, int H, uint64_t seed, int32_t* samples);
+int loop_check_pgo(const double* nodes, int n, const int32_t* edges, const double* meas, const double* weight, int E,
+                   double ell, double lambda0, int max_lm, int max_pcg, double pcg_tol, double cost_tol);
+// a node's incident (edge, side) entries 2 e + side in ascending edge order: start (n + 1), ent (2 E)
+void pgo_build_csr(int n, const int32_t* edges, int E, std::vector<int32_t>& start, std::vector<int32_t>& ent);
+// zinv (E x 8) = the inverse measurements, sw (E) = sqrt(weight)
+void pgo_edge_constants(const double* meas, const double* weight, int E, double* zinv, double* sw);
 // ---- scene rendering (render.hip) ----
 // destroys the context's render events
 void render_release(slam_ctx* c);

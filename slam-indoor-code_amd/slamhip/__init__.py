@@ -37,6 +37,9 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
 from .dense import DenseParams, densify, depth_planes, sweep_matrices
 from .place import Database, LoopParams, Vocabulary, detect_loops, verify_loop
 from . import place
+from . import loopclose
+from .loopclose import (apply_points, close_loops, correct_map, loop_constraints, optimize_pose_graph,
+                        sim3_from_pairs)
 from .video import VideoCapture, VideoWriter, write_mjpeg_avi
 from .config import ConfigError, ConfigService, reference_example
 from .calibration import CalibrationError, chessboard_photos_calibration

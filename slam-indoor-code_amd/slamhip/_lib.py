@@ -49,6 +49,7 @@ KLT_MAX_LEVELS = 9                                     # maxLevel 0..8
 JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = 0, 0x11, 0x21, 0x22      # slam_jpeg_info's sampling
 JPEG_EOF, JPEG_BAD_CODE, JPEG_RUN, JPEG_RESTART = 1, 2, 4, 8       # entropy fault bits of a decode's status
 JPEG_ENC_OVERFLOW, JPEG_ENC_CATEGORY = 1, 2                        # status bits of an encode
+SIM3_OK, SIM3_NO_MODEL, SIM3_TOO_FEW, SIM3_CHOLESKY = range(4)                      # slam_sim3_ransac's status
 VOC_SIFT, VOC_ORB = 0, 1                                           # slam_voc_*'s descriptor kind
 RENDER_POINT, RENDER_LINE, RENDER_FACE = 0, 1, 2                   # the kind in a rendered id (kind << 30 | index)
 RENDER_AUTO, RENDER_THREAD, RENDER_WAVE, RENDER_WAVE_FULL_LIST = 0, 1, 2, 3   # slam_render_views_dev's raster_mode
@@ -230,6 +231,15 @@ SIGNATURES = {
     "slam_voc_train_host": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "slam_bow_vectors_host": (_I, [_P, _P, _I, _P, _I, _P, _P]),
     "slam_bow_score_host": (_I, [_P, _P, _I, _P, _P, _I, _I, _P]),
+    "slam_sim3_ransac_dev": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _D, _U64, _P, _P, _P, _P]),
+    "slam_sim3_ransac": (_I, [_P, _P, _P, _P, _I, _P, _I, _D, _U64, _P, _P, _P, _P]),
+    "slam_sim3_ransac_host": (_I, [_P, _P, _P, _I, _P, _I, _D, _U64, _P, _P, _P, _P]),
+    "slam_pgo_sim3_dev": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _D, _D, _I, _I, _D, _D, _P, _P]),
+    "slam_pgo_sim3": (_I, [_P, _P, _I, _P, _P, _P, _I, _D, _D, _I, _I, _D, _D, _P, _P]),
+    "slam_pgo_sim3_host": (_I, [_P, _I, _P, _P, _P, _I, _D, _D, _I, _I, _D, _D, _P, _P]),
+    "slam_sim3_apply_points_dev": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _P]),
+    "slam_sim3_apply_points": (_I, [_P, _P, _P, _I, _P, _P, _I, _P]),
+    "slam_sim3_apply_points_host": (_I, [_P, _P, _I, _P, _P, _I, _P]),
 }
 
 _lib = None

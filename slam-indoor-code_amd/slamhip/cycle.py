@@ -988,6 +988,7 @@ class Logs:
             self.rotations = open(os.path.join(out_dir, "rotations.txt"), "w")
         self.pose_list, self.rotation_list = [], []
         self.frames = None       # slam_main(dense=...): the good frame of every logged pose
+        self.obs = None          # slam_main(loops=LoopParams(close=True)): per logged pose (xy f32 n x 2, point index i64 n)
 
     def pose(self, R, t, frame=None):
         if self.frames is not None:
@@ -1351,6 +1352,9 @@ def main_cycle(media, K, cond, deque, gd, logs, ops, stats=None):
     processed.append(deque[1].snapshot())
     logs.pose(deque[0].rotation, deque[0].motion, getattr(deque[0], "first_frame", None))
     logs.pose(deque[1].rotation, deque[1].motion, last_good)
+    # loop closing: the frame data of every logged pose, read when their point indices are final (a frame's
+    # after the next frame's push_new_spatial_points, which fills them in place; the last frame's at the end)
+    logged = [deque[0], deque[1]] if logs.obs is not None else None
 
     last = 1
     bidx = FRAME_NOT_FOUND
@@ -1378,6 +1382,8 @@ def main_cycle(media, K, cond, deque, gd, logs, ops, stats=None):
         nxt.motion = np.asarray(tvec, np.float64).reshape(3, 1).copy()
         nxt.rotation = ops.rodrigues(rvec)
         logs.pose(nxt.rotation, nxt.motion, frame)
+        if logged is not None:
+            logged.append(nxt)
 
         p1, p2 = key_point_coords(prev.allExtractedFeatures, nxt.allExtractedFeatures, nxt.allMatches,
                                   prev.undistorted, nxt.undistorted)
@@ -1456,6 +1462,14 @@ def main_cycle(media, K, cond, deque, gd, logs, ops, stats=None):
 
     if pending is not None:             # a loop exit right after a window (PnP's < 4 points)
         pending.finish()
+    if logged is not None:
+        for d in logged:
+            kps = d.allExtractedFeatures
+            idx = getattr(d, "correspondSpatialPointIdx", None)
+            if idx is None or len(idx) != len(kps):      # a frame whose points were never pushed
+                idx = np.full(len(kps), -1, np.int64)
+            logs.obs.append((np.stack([kps["x"], kps["y"]], 1).astype(np.float32).reshape(-1, 2),
+                             np.asarray(idx, np.int64).copy()))
     if processed:
         if cond.useBundleAdjustment:
             bundle_adjustment(K, processed, gd, cond, ops, stats)
@@ -1530,6 +1544,15 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
     score, n_matches, n_inliers, R, t) over the kept frames' indices and, with
     out_dir, to loops.txt: one row `i j score n_matches n_inliers R(9) t(3)` per loop
     in rawOutput's format.  The four result files are unchanged.
+    loops.close (opt-in inside loops): the cycle keeps logs.obs[k] = (xy float32 n x 2, point
+    index int64 n, -1 without a map point) for every logged good frame, the indices into
+    the final gd.spatialPoints; after find_loops, loopclose.close_run matches every kept loop
+    again, builds its Sim(3) constraint, optimises the pose graph and corrects the map.
+    gd.closed holds the result (rotations, motions, points, colors, constraints, dropped,
+    ...); with out_dir, poses_closed.txt, rotations_closed.txt, points_closed.txt and
+    colors_closed.txt are written in rawOutput's format.  Nothing is appended to the four
+    result files or to loops.txt; with no accepted loop the closed files repeat the open
+    ones.  Together with tracker="klt" or undistort="points" it raises ValueError.
     Returns (GlobalData, Logs)."""
     if undistort not in ("frames", "points"):
         raise ValueError('undistort: "frames" or "points"')
@@ -1537,6 +1560,9 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
         raise ValueError('tracker: None or "klt"')
     if tracker is not None and dist is not None:
         raise ValueError("tracker together with dist is not supported")
+    close = loops is not None and getattr(loops, "close", False)
+    if close and (tracker is not None or undistort == "points"):
+        raise ValueError('loops.close together with tracker="klt" or undistort="points" is not supported')
     if _is_fisheye(lens_model) and (dist is None or np.size(dist) != 4):
         raise ValueError('lens_model="fisheye" takes the four coefficients k1 k2 k3 k4 as dist')
     ops = ops or GpuOps()
@@ -1553,6 +1579,8 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
     logs = Logs(out_dir if out_dir is not None else None)
     if dense is not None or loops is not None:
         logs.frames = []
+    if close:
+        logs.obs = []
     gd = GlobalData()
     old, last_id = [], -1
     prefetch = getattr(ops, "prefetched", None)
@@ -1565,8 +1593,13 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
             deque = [TemporalImageData(lens) for _ in range(OPTIMAL_DEQUE_SIZE)]
             define_camera_position(old, last_id, deque[0])
             ngd = GlobalData()
+            n_obs = len(logs.obs) if logs.obs is not None else 0
             last_id = main_cycle(media, K, cond, deque, ngd, logs, ops, stats)
             old = deque
+            if logs.obs is not None:        # this cycle's indices refer to ngd: offset them by the earlier cycles' points
+                base = len(gd.spatialPoints)
+                for _, idx in logs.obs[n_obs:]:
+                    idx[idx >= 0] += base
             gd.push_points(ngd.spatialPoints, ngd.spatialPointsColors)
             gd.cameraRotations += ngd.cameraRotations
             gd.spatialCameraPositions += ngd.spatialCameraPositions
@@ -1600,4 +1633,16 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
             with open(os.path.join(logs.out_dir, "loops.txt"), "w") as f:
                 for i, j, sc, n, inl, R, t in gd.loops:
                     raw_output(np.concatenate([[i, j, sc, n, inl], np.ravel(R), np.ravel(t)]), f)
+        if close:
+            from .loopclose import close_run
+            if len(logs.obs) != len(logs.frames) or len(gd.cameraRotations) != len(logs.frames):
+                raise RuntimeError(f"loops.close: {len(logs.obs)} observation sets and {len(gd.cameraRotations)} final poses "
+                                   f"for {len(logs.frames)} good frames")
+            gd.closed = close_run(gd, logs, K, cond, ops, loops, ctx=getattr(ops, "ctx", None), host=not hasattr(ops, "ctx"))
+            if logs.out_dir:
+                for name, rows in (("poses_closed.txt", gd.closed["motions"]), ("rotations_closed.txt", gd.closed["rotations"]),
+                                   ("points_closed.txt", gd.closed["points"]), ("colors_closed.txt", gd.closed["colors"])):
+                    with open(os.path.join(logs.out_dir, name), "w") as f:
+                        for r in rows:
+                            raw_output(r, f)
     return gd, logs

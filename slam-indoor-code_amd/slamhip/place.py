@@ -457,7 +457,10 @@ def verify_loop(frame_i, kps_i, desc_i, frame_j, kps_j, desc_j, K, cond, ops):
 class LoopParams:
     """slam_main(loops=...): K words trained for `iters` iterations on the run's own keyframes
     (or the vocabulary loaded from the .npz `vocabulary`), candidates by detect_loops(gap, k,
-    alpha), kept when verify_loop finds at least min_inliers."""
+    alpha), kept when verify_loop finds at least min_inliers.  close=True adds the loop-closing
+    stage (loopclose.close_loops over the kept loops): `hypotheses` RANSAC hypotheses per loop,
+    the angular inlier threshold `tau`, at least `min_pairs` pairs and inliers per accepted loop,
+    the optimiser's caps `max_lm` / `max_pcg` and the weight of a loop edge."""
     K: int = 4096
     iters: int = 10
     gap: int = 10
@@ -465,6 +468,13 @@ class LoopParams:
     alpha: float = 0.3
     min_inliers: int = 30
     vocabulary: Optional[str] = None
+    close: bool = False
+    hypotheses: int = 256
+    tau: float = 0.01
+    min_pairs: int = 30
+    max_lm: int = 10
+    max_pcg: int = 400
+    loop_weight: float = 1.0
 
 
 def find_loops(frames, K, cond, ops, prm, ctx=None, host=False):

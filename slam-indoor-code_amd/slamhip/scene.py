@@ -67,17 +67,20 @@ def load_global_data(out_dir, cloud="sparse"):
     Colours are cast with (uchar), i.e. truncated.  Raises ValueError where the
     reference throws: rotation / pose counts or point / colour counts differ.
     cloud="dense" reads dense_points.txt / dense_colors.txt (slam_main(dense=...))
-    in place of the sparse cloud's files."""
-    if cloud not in ("sparse", "dense"):
-        raise ValueError('cloud: "sparse" or "dense"')
+    in place of the sparse cloud's files; cloud="closed" reads the four *_closed.txt
+    files of slam_main(loops=LoopParams(close=True)): corrected cameras and the
+    merged cloud."""
+    if cloud not in ("sparse", "dense", "closed"):
+        raise ValueError('cloud: "sparse" or "dense" (or "closed")')
     prefix = "dense_" if cloud == "dense" else ""
-    poses = _rows(os.path.join(out_dir, "poses.txt"), 3)
-    rotations = _rows(os.path.join(out_dir, "rotations.txt"), 9)
+    suffix = "_closed" if cloud == "closed" else ""
+    poses = _rows(os.path.join(out_dir, "poses" + suffix + ".txt"), 3)
+    rotations = _rows(os.path.join(out_dir, "rotations" + suffix + ".txt"), 9)
     if len(rotations) != len(poses):
         raise ValueError("Count of rotations and translations must be equal: "
                          f"{len(rotations)} rotations, {len(poses)} translations")
-    points = _rows(os.path.join(out_dir, prefix + "points.txt"), 3)
-    colors = _rows(os.path.join(out_dir, prefix + "colors.txt"), 3)
+    points = _rows(os.path.join(out_dir, prefix + "points" + suffix + ".txt"), 3)
+    colors = _rows(os.path.join(out_dir, prefix + "colors" + suffix + ".txt"), 3)
     if len(points) != len(colors):
         raise ValueError("Count of points and their colors must be equal: "
                          f"{len(points)} points, {len(colors)} colors")
@@ -349,7 +352,8 @@ def main(config_path, render=None, cloud="sparse"):
     ("fly_%04d.png", "wwwwaadd") writes one frame per key stroke of scene.fly from the
     reference view, and render = ("fly.avi", keys) encodes those frames where they
     were rendered and writes one Motion-JPEG AVI.  The default writes nothing more.
-    cloud="dense" works on the dense cloud of slam_main(dense=...) instead."""
+    cloud="dense" works on the dense cloud of slam_main(dense=...) instead, cloud="closed"
+    on the corrected cameras and merged cloud of slam_main(loops=LoopParams(close=True))."""
     cfg = ConfigService()
     cfg.setConfigFile(config_path)
     if not cfg.getValue("onlyViz"):
