@@ -15,6 +15,7 @@ namespace slamhip {
 hipError_t DevBuf::ensure(size_t n)
 {
     if (n <= bytes && p) return hipSuccess;
+    if (n > SIZE_MAX - 4095) return hipErrorOutOfMemory;   // a saturated DevLayout: the page rounding below would wrap
     if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
     size_t want = n < 256 ? 256 : n;
     want = (want + 4095) & ~(size_t)4095;
@@ -749,10 +750,13 @@ int slam_orb_detect(slam_ctx* c, const uint8_t* img, int w, int h, size_t step, 
     size_t dstep;
     int rc = upload_image(c, img, w, h, step, channels, &dimg, &dstep);
     if (rc) return rc;
-    const size_t kb = (size_t)std::max(cap, 1) * sizeof(slam_keypoint);
-    SLAM_HIP(c, c->od_out.ensure(kb + (size_t)std::max(cap, 1) * kOrbDescBytes));
-    slam_keypoint* d_kps = c->od_out.as<slam_keypoint>();
-    uint8_t* d_desc = c->od_out.as<uint8_t>() + kb;       // 28 cap bytes in: 4-byte aligned
+    DevLayout lay;
+    const auto s_kps = lay.add<slam_keypoint>((size_t)std::max(cap, 1));
+    const auto s_desc = lay.add<uint8_t>((size_t)std::max(cap, 1) * kOrbDescBytes);
+    DevMem out;
+    SLAM_HIP(c, out.bind(c->od_out, lay));
+    slam_keypoint* d_kps = out.ptr(s_kps);
+    uint8_t* d_desc = out.ptr(s_desc);
     int32_t n = 0;
     if ((rc = orb_detect_batch(c, c->stream, dimg, 1, w, h, channels, nfeatures, (double)scale_factor, nlevels,
                                fast_threshold, score_type, d_kps, cap, &n, desc ? d_desc : nullptr)))
@@ -1455,18 +1459,18 @@ static int undistort_points(slam_ctx* c, const float* src, size_t src_stride, in
     if (int rc = lens_points_params(c, K, dist, ndist, P, max_iter, eps, model, &prm)) return rc;
     if (n == 0) return SLAM_OK;
     SLAM_HIP(c, hipSetDevice(c->device));
-    // device layout: the points at the caller's stride, then n x 2 results, then n residuals
-    const size_t sa = ((size_t)(n - 1) * src_stride + 8 + 15) & ~(size_t)15, sb = (size_t)n * 8, se = (size_t)n * 4;
-    SLAM_HIP(c, c->undist_pts.ensure(sa + sb + se));
-    char* base = c->undist_pts.as<char>();
-    float* d_src = reinterpret_cast<float*>(base);
-    float* d_dst = reinterpret_cast<float*>(base + sa);
-    float* d_err = reinterpret_cast<float*>(base + sa + sb);
-    SLAM_HIP(c, hipMemcpyAsync(d_src, src, (size_t)(n - 1) * src_stride + 8, hipMemcpyHostToDevice, c->stream));
-    SLAM_HIP(c, launch_lens_points(c->stream, prm, d_src, src_stride, n, d_dst, err ? d_err : nullptr));
+    // the points at the caller's stride, then n x 2 results, then n residuals
+    DevLayout lay;
+    const auto s_src = lay.add_strided((size_t)n, src_stride, 2 * sizeof(float));
+    const auto s_dst = lay.add<float>((size_t)n * 2), s_err = lay.add<float>((size_t)n);
+    DevMem d;
+    SLAM_HIP(c, d.bind(c->undist_pts, lay));
+    SLAM_HIP(c, d.upload(s_src, reinterpret_cast<const uint8_t*>(src), c->stream));
+    SLAM_HIP(c, launch_lens_points(c->stream, prm, reinterpret_cast<const float*>(d.ptr(s_src)), src_stride, n, d.ptr(s_dst),
+                                   err ? d.ptr(s_err) : nullptr));
     // dst may be src (stride 8): the upload above is complete before this copy lands
-    SLAM_HIP(c, hipMemcpyAsync(dst, d_dst, sb, hipMemcpyDeviceToHost, c->stream));
-    if (err) SLAM_HIP(c, hipMemcpyAsync(err, d_err, se, hipMemcpyDeviceToHost, c->stream));
+    SLAM_HIP(c, d.download(dst, s_dst, c->stream));
+    if (err) SLAM_HIP(c, d.download(err, s_err, c->stream));
     return stream_sync(c, c->stream);
 }
 
@@ -1649,16 +1653,17 @@ static int corner_subpix_run(slam_ctx* c, hipStream_t s, const uint8_t* d_img, i
         const float y = (float)(i - win_h) / (float)win_h;
         tab[ww + i] = (float)std::exp((double)(-y * y));
     }
-    const size_t cb = (size_t)n * 2 * sizeof(float);
-    SLAM_HIP(c, c->calib_sub.ensure(cb + sizeof(tab)));
-    float* d_corners = c->calib_sub.as<float>();
-    float* d_tab = d_corners + (size_t)n * 2;
-    SLAM_HIP(c, hipMemcpyAsync(d_corners, corners, cb, hipMemcpyHostToDevice, s));
-    SLAM_HIP(c, hipMemcpyAsync(d_tab, tab, (size_t)(ww + wh) * sizeof(float), hipMemcpyHostToDevice, s));
+    DevLayout lay;
+    const auto s_corners = lay.add<float>((size_t)n * 2), s_tab = lay.add<float>((size_t)(ww + wh));
+    DevMem d;
+    SLAM_HIP(c, d.bind(c->calib_sub, lay));
+    float* d_tab = d.ptr(s_tab);
+    SLAM_HIP(c, d.upload(s_corners, corners, s));
+    SLAM_HIP(c, d.upload(s_tab, tab, s));
     // the upload of `tab` (a stack array) must have left it before this function returns: the sync below
-    SLAM_HIP(c, launch_calib_subpix(s, d_img, step, channels, w, h, d_corners, n, win_w, win_h, max_iter, eps, d_tab,
+    SLAM_HIP(c, launch_calib_subpix(s, d_img, step, channels, w, h, d.ptr(s_corners), n, win_w, win_h, max_iter, eps, d_tab,
                                     d_tab + ww));
-    SLAM_HIP(c, hipMemcpyAsync(corners, d_corners, cb, hipMemcpyDeviceToHost, s));
+    SLAM_HIP(c, d.download(corners, s_corners, s));
     return stream_sync(c, s);
 }
 
@@ -2202,36 +2207,31 @@ static int klt_run(slam_ctx* c, hipStream_t s, const uint8_t* d_prev, size_t pre
 {
     const KltLayout L = klt_layout(w, h, a.win_w, a.win_h, a.max_level);
     const size_t tot = (size_t)nframes * n;
-    // prev_pts | next_pts | err | counts | status
-    const size_t o_next = (size_t)n * 2 * sizeof(float), o_err = o_next + tot * 2 * sizeof(float),
-                 o_cnt = o_err + tot * sizeof(float), o_st = o_cnt + (size_t)nframes * sizeof(int32_t);
-    SLAM_HIP(c, c->klt_pts.ensure(o_st + tot));
+    DevLayout lay;
+    const auto s_prev = lay.add<float>((size_t)n * 2), s_next = lay.add<float>(tot * 2), s_err = lay.add<float>(tot);
+    const auto s_cnt = lay.add<int32_t>((size_t)nframes);
+    const auto s_st = lay.add<uint8_t>(tot);
+    DevMem d;
+    SLAM_HIP(c, d.bind(c->klt_pts, lay));
     SLAM_HIP(c, c->klt_pyr.ensure((size_t)(nframes + 1) * L.frame_px));
     SLAM_HIP(c, c->klt_deriv.ensure((size_t)L.frame_px * 2 * sizeof(int16_t)));
-    uint8_t* base = c->klt_pts.as<uint8_t>();
-    float* d_prev_pts = reinterpret_cast<float*>(base);
-    float* d_next = reinterpret_cast<float*>(base + o_next);
-    float* d_err = reinterpret_cast<float*>(base + o_err);
-    int32_t* d_cnt = reinterpret_cast<int32_t*>(base + o_cnt);
-    uint8_t* d_st = base + o_st;
     uint8_t* pyr = c->klt_pyr.as<uint8_t>();
-    SLAM_HIP(c, hipMemcpyAsync(d_prev_pts, prev_pts, o_next, hipMemcpyHostToDevice, s));
-    if (a.flags & SLAM_KLT_USE_INITIAL_FLOW)
-        SLAM_HIP(c, hipMemcpyAsync(d_next, next_pts, tot * 2 * sizeof(float), hipMemcpyHostToDevice, s));
-    SLAM_HIP(c, hipMemsetAsync(d_cnt, 0, (size_t)nframes * sizeof(int32_t), s));
+    SLAM_HIP(c, d.upload(s_prev, prev_pts, s));
+    if (a.flags & SLAM_KLT_USE_INITIAL_FLOW) SLAM_HIP(c, d.upload(s_next, next_pts, s));
+    SLAM_HIP(c, hipMemsetAsync(d.ptr(s_cnt), 0, s_cnt.bytes(), s));
     prof_begin(c, 6, s);
     SLAM_HIP(c, launch_klt_pyramid(s, d_prev, 0, prev_step, channels, 1, L, pyr));
     SLAM_HIP(c, launch_klt_scharr(s, pyr, L, c->klt_deriv.as<int16_t>()));
     SLAM_HIP(c, launch_klt_pyramid(s, d_frames, frame_stride, step, channels, nframes, L, pyr + L.frame_px));
     prof_end(c, 6, s);
     prof_begin(c, 7, s);
-    SLAM_HIP(c, launch_klt_track(s, L, pyr, c->klt_deriv.as<int16_t>(), pyr + L.frame_px, nframes, d_prev_pts, n, d_next,
-                                 d_st, d_err, d_cnt, a.win_w, a.win_h, a.max_count, a.eps2, a.flags, a.min_eig));
+    SLAM_HIP(c, launch_klt_track(s, L, pyr, c->klt_deriv.as<int16_t>(), pyr + L.frame_px, nframes, d.ptr(s_prev), n,
+                                 d.ptr(s_next), d.ptr(s_st), d.ptr(s_err), d.ptr(s_cnt), a.win_w, a.win_h, a.max_count, a.eps2, a.flags, a.min_eig));
     prof_end(c, 7, s);
-    if (next_pts) SLAM_HIP(c, hipMemcpyAsync(next_pts, d_next, tot * 2 * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (status) SLAM_HIP(c, hipMemcpyAsync(status, d_st, tot, hipMemcpyDeviceToHost, s));
-    if (err) SLAM_HIP(c, hipMemcpyAsync(err, d_err, tot * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (counts) SLAM_HIP(c, hipMemcpyAsync(counts, d_cnt, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (next_pts) SLAM_HIP(c, d.download(next_pts, s_next, s));
+    if (status) SLAM_HIP(c, d.download(status, s_st, s));
+    if (err) SLAM_HIP(c, d.download(err, s_err, s));
+    if (counts) SLAM_HIP(c, d.download(counts, s_cnt, s));
     return stream_sync(c, s);
 }
 

@@ -1565,54 +1565,58 @@ int ba_solve(slam_ctx* c, double* K4, int nf, double* ext6, int np, double* pts3
     const int nwp = (int)std::max({gobs, gpt128, gupd});
 
     // ---- device layout ----
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    DevLayout lay;
     // the uploaded arrays first: one pinned image, one copy
-    const size_t o_rof = carve(4 * (size_t)no), o_roxy = carve(16 * (size_t)no), o_qsrc = carve(4 * (size_t)no),
-                 o_por = carve(4 * (size_t)std::max(np, 1)), o_xin = carve(8 * (size_t)NX),
-                 o_ps = carve(4 * (size_t)(np + 1)), o_fl = carve(4 * (size_t)no),
-                 o_gch = carve(sizeof(Chunk) * std::max(1, ngch)), o_gcs = carve(4 * gcs.size()),
-                 o_pch = carve(sizeof(PtChunk) * std::max(1, npch)),
-                 o_gf = carve(4 * gframes.size()), o_bs = carve(4 * bstart.size()), o_bl = carve(4 * bpos.size()),
-                 o_fps = carve(4 * fpstart.size()), o_fpl = carve(4 * fppos.size()),
-                 o_st = carve(sizeof(BaState));
-    const size_t up_bytes = off;
-    const size_t o_of = carve(4 * (size_t)no), o_op = carve(4 * (size_t)no), o_oxy = carve(16 * (size_t)no),
-                 o_x0 = carve(8 * (size_t)NX), o_xout = carve(8 * (size_t)NX),
-                 o_x1 = carve(8 * (size_t)NX), o_r0 = carve(16 * (size_t)no),
-                 o_r1 = carve(16 * (size_t)no), o_J0 = carve(8 * 2 * NJ * (size_t)no),
-                 o_J1 = carve(8 * 2 * NJ * (size_t)no), o_g0 = carve(8 * (size_t)N), o_g1 = carve(8 * (size_t)N),
-                 o_u0 = carve(8 * (size_t)kBlk * nf), o_u1 = carve(8 * (size_t)kBlk * nf), o_sc = carve(8 * (size_t)N),
-                 o_vi = carve(72 * (size_t)std::max(np, 1)), o_yc = carve(8 * (size_t)nc),
-                 o_sg = carve(8 * (size_t)E),
-                 o_sp = carve(8 * (size_t)kBlk * std::max(nparts, 1)), o_bk = carve(8 * (size_t)kBlk * nb2),
-                 o_gp = carve(8 * (size_t)kBlk * std::max({ngch, nfp, 1})),
-                 o_wp = carve(64 * (size_t)nwp);
+    const auto s_rof = lay.add<int>((size_t)no);
+    const auto s_roxy = lay.add<double>(2 * (size_t)no);
+    const auto s_qsrc = lay.add<int>((size_t)no), s_por = lay.add<int>((size_t)std::max(np, 1));
+    const auto s_xin = lay.add<double>((size_t)NX);
+    const auto s_ps = lay.add<int>((size_t)np + 1), s_fl = lay.add<int>((size_t)no);
+    const auto s_gch = lay.add<Chunk>((size_t)std::max(1, ngch));
+    const auto s_gcs = lay.add<int>(gcs.size());
+    const auto s_pch = lay.add<PtChunk>((size_t)std::max(1, npch));
+    const auto s_gf = lay.add<int>(gframes.size()), s_bs = lay.add<int>(bstart.size()), s_bl = lay.add<int>(bpos.size());
+    const auto s_fps = lay.add<int>(fpstart.size()), s_fpl = lay.add<int>(fppos.size());
+    const auto s_st = lay.add<BaState>(1);
+    const size_t up_bytes = lay.bytes();
+    const auto s_of = lay.add<int>((size_t)no), s_op = lay.add<int>((size_t)no);
+    const auto s_oxy = lay.add<double>(2 * (size_t)no);
+    const auto s_x0 = lay.add<double>((size_t)NX), s_xout = lay.add<double>((size_t)NX), s_x1 = lay.add<double>((size_t)NX);
+    const auto s_r0 = lay.add<double>(2 * (size_t)no), s_r1 = lay.add<double>(2 * (size_t)no);
+    const auto s_J0 = lay.add<double>(2 * NJ * (size_t)no), s_J1 = lay.add<double>(2 * NJ * (size_t)no);
+    const auto s_g0 = lay.add<double>((size_t)N), s_g1 = lay.add<double>((size_t)N);
+    const auto s_u0 = lay.add<double>((size_t)kBlk * nf), s_u1 = lay.add<double>((size_t)kBlk * nf);
+    const auto s_sc = lay.add<double>((size_t)N);
+    const auto s_vi = lay.add<double>(9 * (size_t)std::max(np, 1));
+    const auto s_yc = lay.add<double>((size_t)nc), s_sg = lay.add<double>((size_t)E);
+    const auto s_sp = lay.add<double>((size_t)kBlk * std::max(nparts, 1)), s_bk = lay.add<double>((size_t)kBlk * nb2);
+    const auto s_gp = lay.add<double>((size_t)kBlk * std::max({ngch, nfp, 1}));
+    const auto s_wp = lay.add<double>(8 * (size_t)nwp);
     // pinned host space: the upload image, then the state readbacks and the final x
     char* pin = static_cast<char*>(readback(c, up_bytes + 2 * sizeof(BaState) + 8 * (size_t)NX));
     if (!pin) return set_err(c, SLAM_E_HIP, "pinned staging allocation failed");
     BaState* hst = reinterpret_cast<BaState*>(pin + up_bytes);
     double* hx = reinterpret_cast<double*>(pin + up_bytes + 2 * sizeof(BaState));
-    SLAM_HIP(c, c->ba_par.ensure(off));
-    char* base = c->ba_par.as<char>();
+    DevMem dm;
+    SLAM_HIP(c, dm.bind(c->ba_par, lay));
     BaDev d;
     d.nf = nf; d.np = np; d.no = no; d.nc = nc; d.N = N; d.NX = NX; d.loss = loss; d.a = a;
-    d.of = (const int*)(base + o_of); d.op = (const int*)(base + o_op); d.oxy = (const double*)(base + o_oxy);
-    d.pstart = (const int*)(base + o_ps); d.flist = (const int*)(base + o_fl);
-    d.gch = (const Chunk*)(base + o_gch); d.gcs = (const int*)(base + o_gcs);
-    d.pch = (const PtChunk*)(base + o_pch);
-    d.gframes = (const int*)(base + o_gf); d.bstart = (const int*)(base + o_bs); d.bpos = (const int*)(base + o_bl);
-    d.fpstart = (const int*)(base + o_fps); d.fppos = (const int*)(base + o_fpl);
-    d.x[0] = (double*)(base + o_x0); d.x[1] = (double*)(base + o_x1);
-    d.r[0] = (double*)(base + o_r0); d.r[1] = (double*)(base + o_r1);
-    d.J[0] = (double*)(base + o_J0); d.J[1] = (double*)(base + o_J1);
-    d.g[0] = (double*)(base + o_g0); d.g[1] = (double*)(base + o_g1);
-    d.blkU[0] = (double*)(base + o_u0); d.blkU[1] = (double*)(base + o_u1);
-    d.scale = (double*)(base + o_sc); d.Vinv = (double*)(base + o_vi); d.yc = (double*)(base + o_yc);
-    d.Sg = (double*)(base + o_sg);
-    d.spart = (double*)(base + o_sp); d.blkS = (double*)(base + o_bk); d.gpart = (double*)(base + o_gp);
-    d.wpart = (double*)(base + o_wp);
-    d.st = (BaState*)(base + o_st);
+    d.of = dm.ptr(s_of); d.op = dm.ptr(s_op); d.oxy = dm.ptr(s_oxy);
+    d.pstart = dm.ptr(s_ps); d.flist = dm.ptr(s_fl);
+    d.gch = dm.ptr(s_gch); d.gcs = dm.ptr(s_gcs);
+    d.pch = dm.ptr(s_pch);
+    d.gframes = dm.ptr(s_gf); d.bstart = dm.ptr(s_bs); d.bpos = dm.ptr(s_bl);
+    d.fpstart = dm.ptr(s_fps); d.fppos = dm.ptr(s_fpl);
+    d.x[0] = dm.ptr(s_x0); d.x[1] = dm.ptr(s_x1);
+    d.r[0] = dm.ptr(s_r0); d.r[1] = dm.ptr(s_r1);
+    d.J[0] = dm.ptr(s_J0); d.J[1] = dm.ptr(s_J1);
+    d.g[0] = dm.ptr(s_g0); d.g[1] = dm.ptr(s_g1);
+    d.blkU[0] = dm.ptr(s_u0); d.blkU[1] = dm.ptr(s_u1);
+    d.scale = dm.ptr(s_sc); d.Vinv = dm.ptr(s_vi); d.yc = dm.ptr(s_yc);
+    d.Sg = dm.ptr(s_sg);
+    d.spart = dm.ptr(s_sp); d.blkS = dm.ptr(s_bk); d.gpart = dm.ptr(s_gp);
+    d.wpart = dm.ptr(s_wp);
+    d.st = dm.ptr(s_st);
 
     BaState st0;
     std::memset(&st0, 0, sizeof(st0));
@@ -1621,26 +1625,27 @@ int ba_solve(slam_ctx* c, double* K4, int nf, double* ext6, int np, double* pts3
     st0.xnorm = xnorm;
     st0.max_iters = max_iters;
     st0.usable = 1;
-    auto put = [&](size_t o, const void* src, size_t bytes) { if (bytes) std::memcpy(pin + o, src, bytes); };
-    put(o_rof, of, 4 * (size_t)no);
-    put(o_roxy, oxy, 16 * (size_t)no);
-    put(o_qsrc, qsrc.data(), 4 * (size_t)no);
-    put(o_por, porder.data(), 4 * (size_t)np);
-    put(o_xin, K4, 32);
-    put(o_xin + 32, ext6, sizeof(double) * 6 * nf);
-    put(o_xin + 32 + sizeof(double) * 6 * nf, pts3, sizeof(double) * 3 * np);
-    put(o_ps, qstart.data(), 4 * (size_t)(np + 1));
-    put(o_fl, flist.data(), 4 * (size_t)no);
-    put(o_gch, gch.data(), sizeof(Chunk) * ngch);
-    put(o_gcs, gcs.data(), 4 * gcs.size());
-    put(o_pch, pch.data(), sizeof(PtChunk) * npch);
-    put(o_gf, gframes.data(), 4 * gframes.size());
-    put(o_bs, bstart.data(), 4 * bstart.size());
-    put(o_bl, bpos.data(), 4 * bpos.size());
-    put(o_fps, fpstart.data(), 4 * fpstart.size());
-    put(o_fpl, fppos.data(), 4 * fppos.size());
-    put(o_st, &st0, sizeof(st0));
-    SLAM_HIP(c, hipMemcpyAsync(base, pin, up_bytes, hipMemcpyHostToDevice, s));
+    // the image mirrors the device layout up to up_bytes: a slot's place in it
+    auto img = [&](auto slot) { return reinterpret_cast<decltype(dm.ptr(slot))>(pin + slot.off); };
+    std::copy_n(of, no, img(s_rof));
+    std::copy_n(oxy, 2 * (size_t)no, img(s_roxy));
+    std::copy_n(qsrc.data(), no, img(s_qsrc));
+    std::copy_n(porder.data(), np, img(s_por));
+    std::copy_n(K4, 4, img(s_xin));
+    std::copy_n(ext6, 6 * (size_t)nf, img(s_xin) + 4);
+    std::copy_n(pts3, 3 * (size_t)np, img(s_xin) + 4 + 6 * (size_t)nf);
+    std::copy_n(qstart.data(), np + 1, img(s_ps));
+    std::copy_n(flist.data(), no, img(s_fl));
+    std::copy_n(gch.data(), ngch, img(s_gch));
+    std::copy_n(gcs.data(), gcs.size(), img(s_gcs));
+    std::copy_n(pch.data(), npch, img(s_pch));
+    std::copy_n(gframes.data(), gframes.size(), img(s_gf));
+    std::copy_n(bstart.data(), bstart.size(), img(s_bs));
+    std::copy_n(bpos.data(), bpos.size(), img(s_bl));
+    std::copy_n(fpstart.data(), fpstart.size(), img(s_fps));
+    std::copy_n(fppos.data(), fppos.size(), img(s_fpl));
+    *img(s_st) = st0;
+    SLAM_HIP(c, hipMemcpyAsync(dm.base, pin, up_bytes, hipMemcpyHostToDevice, s));
     // (every bucket / frame block is written by its reduction, empty ones as 0)
     BA_T(2);
 
@@ -1656,14 +1661,12 @@ int ba_solve(slam_ctx* c, double* K4, int nf, double* ext6, int np, double* pts3
     };
 
     // ---- iteration 0: cost + Jacobian, Jacobi scaling, gradient check ----
-    const int* dgcs = (const int*)(base + o_gcs);
-    const int* dbs = (const int*)(base + o_bs);
-    (void)dgcs;
-    const int* dpor = (const int*)(base + o_por);
-    double* dxout = (double*)(base + o_xout);
+    const int* dbs = dm.ptr(s_bs);
+    const int* dpor = dm.ptr(s_por);
+    double* dxout = dm.ptr(s_xout);
     hipLaunchKernelGGL(ba_import, dim3((std::max(np, 4 + 6 * nf) + 127) / 128), dim3(128), 0, s, d,
-                       (const int*)(base + o_rof), (const double*)(base + o_roxy), (const int*)(base + o_qsrc), dpor,
-                       (const double*)(base + o_xin));
+                       (const int*)dm.ptr(s_rof), (const double*)dm.ptr(s_roxy), (const int*)dm.ptr(s_qsrc), dpor,
+                       (const double*)dm.ptr(s_xin));
     hipLaunchKernelGGL(ba_eval_init, dim3(gobs), dim3(128), 0, s, d);
     hipLaunchKernelGGL(ba_gram<kGramUnscaled>, dim3(ngch), dim3(128), 0, s, d);
     hipLaunchKernelGGL(ba_frame_reduce<kGramUnscaled>, dim3(nf), dim3(1024), 0, s, d);
@@ -1712,7 +1715,7 @@ int ba_solve(slam_ctx* c, double* K4, int nf, double* ext6, int np, double* pts3
     hipLaunchKernelGGL(ba_export, dim3((std::max(np, 4 + 6 * nf) + 127) / 128), dim3(128), 0, s, d, dpor, dxout);
     SLAM_HIP(c, hipGetLastError());
     SLAM_HIP(c, hipMemcpyAsync(hst + 1, d.st, sizeof(BaState), hipMemcpyDeviceToHost, s));
-    SLAM_HIP(c, hipMemcpyAsync(hx, dxout, 8 * (size_t)NX, hipMemcpyDeviceToHost, s));
+    SLAM_HIP(c, dm.download(hx, s_xout, s));
     {
         int rc = stream_sync(c, s, true);
         if (rc) return rc;

@@ -300,9 +300,14 @@ __global__ __launch_bounds__(256) void plane_project(const float* __restrict__ p
     out[2 * i + 1] = (float)(az * coef);
 }
 
-// cluster workspace layout: [0, 16) pair counters {exact-path pairs}, then plane scratch
-constexpr size_t kPlaneOff = 256;
-constexpr size_t kPlaneBytes = (size_t)(kPlaneBlocks + 4) * kPlaneSums * sizeof(double);
+// cluster workspace: the pair counters {exact-path pairs} first (slam_cluster_last_stats reads them at the
+// buffer's start), then the plane fit's block slots and its results (sum 9, moments 9, mean 3)
+struct ClusterWs {
+    DevLayout lay;
+    Slot<unsigned long long> stats = lay.add<unsigned long long>(2);
+    Slot<double> slots = lay.add<double>((size_t)kPlaneBlocks * kPlaneSums);
+    Slot<double> res = lay.add<double>(2 * kPlaneSums + 3);
+};
 
 int cluster_dev(slam_ctx* c, hipStream_t s, const float* d_pts, const uint8_t* d_colors, int n, float max_distance,
                 float euclid_weight, float color_weight, int32_t* d_labels)
@@ -316,9 +321,11 @@ int cluster_dev(slam_ctx* c, hipStream_t s, const float* d_pts, const uint8_t* d
     p.dw = (double)euclid_weight;
     p.cw = (double)color_weight;
     cluster_rejects(p);
-    SLAM_HIP(c, c->cluster.ensure(kPlaneOff + kPlaneBytes));
-    unsigned long long* stats = c->cluster.as<unsigned long long>();
-    SLAM_HIP(c, hipMemsetAsync(stats, 0, 16, s));
+    const ClusterWs L;
+    DevMem ws;
+    SLAM_HIP(c, ws.bind(c->cluster, L.lay));
+    unsigned long long* stats = ws.ptr(L.stats);
+    SLAM_HIP(c, hipMemsetAsync(stats, 0, L.stats.bytes(), s));
     const int nb = (n + 255) / 256;
     hipLaunchKernelGGL(cluster_init, dim3(nb), dim3(256), 0, s, d_labels, n);
     hipLaunchKernelGGL(cluster_pairs, dim3((unsigned)npairs), dim3(kTile), 0, s, d_pts, d_colors, n, p, d_labels, stats);
@@ -333,15 +340,15 @@ int cluster_dev(slam_ctx* c, hipStream_t s, const float* d_pts, const uint8_t* d
 int plane_moments(slam_ctx* c, const float* pts, int n, double* sum, double* mean, double* mom)
 {
     hipStream_t s = c->stream;
-    const size_t pb = (size_t)n * 3 * sizeof(float);
-    SLAM_HIP(c, c->cluster.ensure(kPlaneOff + kPlaneBytes));
-    SLAM_HIP(c, c->geom.ensure(pb));
-    float* d_pts = c->geom.as<float>();
-    double* slots = reinterpret_cast<double*>(c->cluster.as<char>() + kPlaneOff);
-    double* d_sum = slots + (size_t)kPlaneBlocks * kPlaneSums;      // 9
-    double* d_mom = d_sum + kPlaneSums;                              // 9
-    double* d_mean = d_mom + kPlaneSums;                             // 3
-    SLAM_HIP(c, hipMemcpyAsync(d_pts, pts, pb, hipMemcpyHostToDevice, s));
+    const ClusterWs L;
+    DevLayout lin;
+    const auto s_pts = lin.add<float>((size_t)n * 3);
+    DevMem ws, in;
+    SLAM_HIP(c, ws.bind(c->cluster, L.lay));
+    SLAM_HIP(c, in.bind(c->geom, lin));
+    float* d_pts = in.ptr(s_pts);
+    double *slots = ws.ptr(L.slots), *d_sum = ws.ptr(L.res), *d_mom = d_sum + kPlaneSums, *d_mean = d_mom + kPlaneSums;
+    SLAM_HIP(c, in.upload(s_pts, pts, s));
     const int nb = std::min(kPlaneBlocks, (n + 255) / 256);
     hipLaunchKernelGGL(plane_reduce, dim3(nb), dim3(256), 0, s, d_pts, n, (const double*)nullptr, slots);
     hipLaunchKernelGGL(plane_sum_slots, dim3(1), dim3(64), 0, s, slots, nb, n, d_sum, d_mean);
@@ -349,7 +356,7 @@ int plane_moments(slam_ctx* c, const float* pts, int n, double* sum, double* mea
     hipLaunchKernelGGL(plane_sum_slots, dim3(1), dim3(64), 0, s, slots, nb, n, d_mom, (double*)nullptr);
     SLAM_HIP(c, hipGetLastError());
     double h[2 * kPlaneSums + 3];
-    SLAM_HIP(c, hipMemcpyAsync(h, d_sum, sizeof(h), hipMemcpyDeviceToHost, s));
+    SLAM_HIP(c, ws.download(h, L.res, s));
     SLAM_HIP(c, hipStreamSynchronize(s));
     for (int k = 0; k < 3; k++) { sum[k] = h[k]; mean[k] = h[2 * kPlaneSums + k]; }
     for (int k = 0; k < 6; k++) mom[k] = h[kPlaneSums + 3 + k];
@@ -382,17 +389,17 @@ int slam_cluster_points(slam_ctx* c, const float* pts, const uint8_t* colors, in
     if (n == 0) return SLAM_OK;
     SLAM_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const size_t pb = ((size_t)n * 12 + 255) & ~(size_t)255, cb = ((size_t)n * 3 + 255) & ~(size_t)255;
-    SLAM_HIP(c, c->geom.ensure(pb + cb + (size_t)n * 4));
-    char* base = c->geom.as<char>();
-    float* d_pts = reinterpret_cast<float*>(base);
-    uint8_t* d_col = reinterpret_cast<uint8_t*>(base + pb);
-    int32_t* d_lab = reinterpret_cast<int32_t*>(base + pb + cb);
-    SLAM_HIP(c, hipMemcpyAsync(d_pts, pts, (size_t)n * 12, hipMemcpyHostToDevice, s));
-    SLAM_HIP(c, hipMemcpyAsync(d_col, colors, (size_t)n * 3, hipMemcpyHostToDevice, s));
-    const int rc = cluster_dev(c, s, d_pts, d_col, n, max_distance, euclid_weight, color_weight, d_lab);
+    DevLayout lay;
+    const auto s_pts = lay.add<float>((size_t)n * 3);
+    const auto s_col = lay.add<uint8_t>((size_t)n * 3);
+    const auto s_lab = lay.add<int32_t>((size_t)n);
+    DevMem d;
+    SLAM_HIP(c, d.bind(c->geom, lay));
+    SLAM_HIP(c, d.upload(s_pts, pts, s));
+    SLAM_HIP(c, d.upload(s_col, colors, s));
+    const int rc = cluster_dev(c, s, d.ptr(s_pts), d.ptr(s_col), n, max_distance, euclid_weight, color_weight, d.ptr(s_lab));
     if (rc != SLAM_OK) return rc;
-    SLAM_HIP(c, hipMemcpyAsync(labels, d_lab, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    SLAM_HIP(c, d.download(labels, s_lab, s));
     SLAM_HIP(c, hipStreamSynchronize(s));
     int comps = 0;
     for (int i = 0; i < n; i++) comps += labels[i] == i;
@@ -450,15 +457,15 @@ int slam_project_to_plane(slam_ctx* c, const float* pts, int n, const float* cen
     if (n == 0) return SLAM_OK;
     SLAM_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const size_t pb = ((size_t)n * 12 + 255) & ~(size_t)255;
-    SLAM_HIP(c, c->geom.ensure(pb + (size_t)n * 8));
-    float* d_pts = c->geom.as<float>();
-    float* d_out = reinterpret_cast<float*>(c->geom.as<char>() + pb);
-    SLAM_HIP(c, hipMemcpyAsync(d_pts, pts, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    DevLayout lay;
+    const auto s_pts = lay.add<float>((size_t)n * 3), s_out = lay.add<float>((size_t)n * 2);
+    DevMem d;
+    SLAM_HIP(c, d.bind(c->geom, lay));
+    SLAM_HIP(c, d.upload(s_pts, pts, s));
     ProjectParams p{centroid[0], centroid[1], centroid[2], normal[0], normal[1], normal[2]};
-    hipLaunchKernelGGL(plane_project, dim3((n + 255) / 256), dim3(256), 0, s, d_pts, n, p, d_out);
+    hipLaunchKernelGGL(plane_project, dim3((n + 255) / 256), dim3(256), 0, s, d.ptr(s_pts), n, p, d.ptr(s_out));
     SLAM_HIP(c, hipGetLastError());
-    SLAM_HIP(c, hipMemcpyAsync(out_xy, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    SLAM_HIP(c, d.download(out_xy, s_out, s));
     SLAM_HIP(c, hipStreamSynchronize(s));
     return SLAM_OK;
 }

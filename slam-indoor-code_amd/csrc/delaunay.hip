@@ -57,8 +57,6 @@ namespace {
 
 constexpr float kSubdivRange = 100000.f;      // Subdiv2D(Rect(-100000, -100000, 200000, 200000))
 constexpr int kWavesPerBlock = 4;
-constexpr size_t kHdrBytes = 256;
-
 struct DelaunayHdr {
     unsigned long long pred, exact, ties;     // predicates evaluated, of those on the exact path, tie passes
     int bad;                                  // a non-finite or out-of-range coordinate was seen
@@ -353,12 +351,15 @@ int delaunay_run(slam_ctx* c, hipStream_t s, const float* d_xy, int n, int32_t* 
     *count = 0;
     if (n > (1 << 29)) return set_err(c, SLAM_E_UNSUPPORTED, "slam_delaunay_2d: n > 2^29");
     const int tri_cap = std::max(256, next_pow2(2ll * n));      // >= 2n - 5, and a whole number of sort tiles
-    const size_t dup_bytes = ((size_t)n + 255) & ~(size_t)255;
-    SLAM_HIP(c, c->delaunay.ensure(kHdrBytes + dup_bytes + (size_t)tri_cap * sizeof(Tri)));
-    char* base = c->delaunay.as<char>();
-    DelaunayHdr* hdr = reinterpret_cast<DelaunayHdr*>(base);
-    uint8_t* dup = reinterpret_cast<uint8_t*>(base + kHdrBytes);
-    Tri* tris = reinterpret_cast<Tri*>(base + kHdrBytes + dup_bytes);
+    DevLayout lay;
+    const auto s_hdr = lay.add<DelaunayHdr>(1);       // first: slam_delaunay_last_stats reads it at the buffer's start
+    const auto s_dup = lay.add<uint8_t>((size_t)n);
+    const auto s_tris = lay.add<Tri>((size_t)tri_cap);
+    DevMem ws;
+    SLAM_HIP(c, ws.bind(c->delaunay, lay));
+    DelaunayHdr* hdr = ws.ptr(s_hdr);
+    uint8_t* dup = ws.ptr(s_dup);
+    Tri* tris = ws.ptr(s_tris);
     const float2* xy = reinterpret_cast<const float2*>(d_xy);
 
     SLAM_HIP(c, hipMemsetAsync(hdr, 0, sizeof(DelaunayHdr), s));
@@ -432,18 +433,19 @@ int slam_delaunay_2d(slam_ctx* c, const float* xy, int n, int32_t* tris, int cap
     if (n == 0) return SLAM_OK;
     SLAM_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const size_t xb = ((size_t)n * 8 + 255) & ~(size_t)255;
     const size_t keep = (size_t)std::min<long long>(cap, std::max(256ll, 4ll * n));   // >= the scratch capacity of delaunay_run
-    SLAM_HIP(c, c->geom.ensure(xb + std::max<size_t>(keep, 1) * sizeof(Tri)));
-    float* d_xy = c->geom.as<float>();
-    int32_t* d_tris = reinterpret_cast<int32_t*>(c->geom.as<char>() + xb);
-    SLAM_HIP(c, hipMemcpyAsync(d_xy, xy, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    DevLayout lay;
+    const auto s_xy = lay.add<float>((size_t)n * 2);
+    const auto s_tris = lay.add<int32_t>(keep * 3);
+    DevMem d;
+    SLAM_HIP(c, d.bind(c->geom, lay));
+    SLAM_HIP(c, d.upload(s_xy, xy, s));
     int count = 0;
-    const int rc = delaunay_run(c, s, d_xy, n, d_tris, cap, nullptr, &count);
+    const int rc = delaunay_run(c, s, d.ptr(s_xy), n, d.ptr(s_tris), cap, nullptr, &count);
     *n_tris = count;
     if (rc != SLAM_OK) return rc;
     if (count) {
-        SLAM_HIP(c, hipMemcpyAsync(tris, d_tris, (size_t)count * sizeof(Tri), hipMemcpyDeviceToHost, s));
+        SLAM_HIP(c, d.download(tris, s_tris, (size_t)count * 3, s));
         SLAM_HIP(c, hipStreamSynchronize(s));
     }
     return SLAM_OK;
@@ -473,19 +475,19 @@ int slam_delaunay_predicates(slam_ctx* c, const uint8_t* kind, const float* vals
     if (n == 0) return SLAM_OK;
     SLAM_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const size_t nb = ((size_t)n + 255) & ~(size_t)255, vb = (size_t)n * 8 * sizeof(float);
-    SLAM_HIP(c, c->geom.ensure(vb + 3 * nb));
-    char* base = c->geom.as<char>();
-    float* d_vals = reinterpret_cast<float*>(base);
-    uint8_t* d_kind = reinterpret_cast<uint8_t*>(base + vb);
-    int8_t* d_fs = reinterpret_cast<int8_t*>(base + vb + nb);
-    int8_t* d_s = reinterpret_cast<int8_t*>(base + vb + 2 * nb);
-    SLAM_HIP(c, hipMemcpyAsync(d_vals, vals, vb, hipMemcpyHostToDevice, s));
-    SLAM_HIP(c, hipMemcpyAsync(d_kind, kind, (size_t)n, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(predicate_cases, dim3((n + 63) / 64), dim3(64), 0, s, d_kind, d_vals, n, d_fs, d_s);
+    DevLayout lay;
+    const auto s_vals = lay.add<float>((size_t)n * 8);
+    const auto s_kind = lay.add<uint8_t>((size_t)n);
+    const auto s_fs = lay.add<int8_t>((size_t)n), s_sign = lay.add<int8_t>((size_t)n);
+    DevMem d;
+    SLAM_HIP(c, d.bind(c->geom, lay));
+    SLAM_HIP(c, d.upload(s_vals, vals, s));
+    SLAM_HIP(c, d.upload(s_kind, kind, s));
+    hipLaunchKernelGGL(predicate_cases, dim3((n + 63) / 64), dim3(64), 0, s, d.ptr(s_kind), d.ptr(s_vals), n, d.ptr(s_fs),
+                       d.ptr(s_sign));
     SLAM_HIP(c, hipGetLastError());
-    SLAM_HIP(c, hipMemcpyAsync(filter_sign, d_fs, (size_t)n, hipMemcpyDeviceToHost, s));
-    SLAM_HIP(c, hipMemcpyAsync(sign, d_s, (size_t)n, hipMemcpyDeviceToHost, s));
+    SLAM_HIP(c, d.download(filter_sign, s_fs, s));
+    SLAM_HIP(c, d.download(sign, s_sign, s));
     SLAM_HIP(c, hipStreamSynchronize(s));
     return SLAM_OK;
 }

@@ -503,25 +503,25 @@ int relative_pose(slam_ctx* c, const float* p1, const float* p2, int n, const do
     } else {
         ransac_subsets5(n, kMaxIters, sub.data());
     }
-    // device layout
-    size_t off = 0;
-    auto carve = [&](size_t b) { const size_t o = off; off += (b + 255) & ~(size_t)255; return o; };
-    const size_t o_q = carve(sizeof(double4) * (size_t)n), o_sub = carve(sizeof(int) * 5 * kMaxIters),
-                 o_es = carve(sizeof(double) * 9 * kMaxModels * kMaxIters), o_nm = carve(sizeof(int) * kMaxIters),
-                 o_ct = carve(sizeof(int) * kMaxModels * kMaxIters), o_e = carve(sizeof(double) * 9),
-                 o_mask = carve((size_t)n), o_bits = carve((size_t)n);
-    SLAM_HIP(c, c->geom.ensure(off));
-    char* base = c->geom.as<char>();
+    DevLayout lay;
+    const auto s_q = lay.add<double4>((size_t)n);
+    const auto s_sub = lay.add<int>((size_t)5 * kMaxIters);
+    const auto s_es = lay.add<double>((size_t)9 * kMaxModels * kMaxIters);
+    const auto s_nm = lay.add<int>((size_t)kMaxIters), s_ct = lay.add<int>((size_t)kMaxModels * kMaxIters);
+    const auto s_e = lay.add<double>(9);
+    const auto s_mask = lay.add<uint8_t>((size_t)n), s_bits = lay.add<uint8_t>((size_t)n);
+    DevMem d;
+    SLAM_HIP(c, d.bind(c->geom, lay));
     EpParams ep;
-    ep.q = reinterpret_cast<const double4*>(base + o_q);
+    ep.q = d.ptr(s_q);
     ep.n = n;
-    ep.subsets = reinterpret_cast<const int*>(base + o_sub);
-    ep.Es = reinterpret_cast<double*>(base + o_es);
-    ep.nmodels = reinterpret_cast<int*>(base + o_nm);
-    ep.counts = reinterpret_cast<int*>(base + o_ct);
+    ep.subsets = d.ptr(s_sub);
+    ep.Es = d.ptr(s_es);
+    ep.nmodels = d.ptr(s_nm);
+    ep.counts = d.ptr(s_ct);
     ep.thr2 = thr2;
-    SLAM_HIP(c, hipMemcpyAsync(base + o_q, q.data(), sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice, s));
-    SLAM_HIP(c, hipMemcpyAsync(base + o_sub, sub.data(), sizeof(int) * 5 * kMaxIters, hipMemcpyHostToDevice, s));
+    SLAM_HIP(c, d.upload(s_q, reinterpret_cast<const double4*>(q.data()), s));
+    SLAM_HIP(c, d.upload(s_sub, sub.data(), s));
     std::vector<int> nm(kMaxIters, 0), ct((size_t)kMaxModels * kMaxIters, 0);
     // The hypotheses in chunks (64, 256, then the rest), each replayed before the
     // next is launched: RANSACUpdateNumIters only lowers niters, so the loop
@@ -563,10 +563,9 @@ int relative_pose(slam_ctx* c, const float* p1, const float* p2, int n, const do
     if (best_it < 0) return SLAM_OK;
     double E[9];
     SLAM_HIP(c, hipMemcpy(E, ep.Es + ((size_t)best_it * kMaxModels + best_m) * 9, sizeof(E), hipMemcpyDeviceToHost));
-    double* dE = reinterpret_cast<double*>(base + o_e);
-    uint8_t* dmask = reinterpret_cast<uint8_t*>(base + o_mask);
-    uint8_t* dbits = reinterpret_cast<uint8_t*>(base + o_bits);
-    SLAM_HIP(c, hipMemcpyAsync(dE, E, sizeof(E), hipMemcpyHostToDevice, s));
+    double* dE = d.ptr(s_e);
+    uint8_t *dmask = d.ptr(s_mask), *dbits = d.ptr(s_bits);
+    SLAM_HIP(c, d.upload(s_e, E, s));
     if (n == 5) SLAM_HIP(c, hipMemsetAsync(dmask, 1, 5, s));
     else hipLaunchKernelGGL(ep_mask, dim3((n + 255) / 256), dim3(256), 0, s, ep.q, n, (const double*)dE, thr2, dmask);
     // recoverPose
@@ -576,8 +575,8 @@ int relative_pose(slam_ctx* c, const float* p1, const float* p2, int n, const do
     hipLaunchKernelGGL(ep_cheir, dim3((n + 127) / 128), dim3(128), 0, s, cp);
     SLAM_HIP(c, hipGetLastError());
     std::vector<uint8_t> bits((size_t)n);
-    if (ransac_mask) SLAM_HIP(c, hipMemcpyAsync(ransac_mask, dmask, (size_t)n, hipMemcpyDeviceToHost, s));
-    SLAM_HIP(c, hipMemcpyAsync(bits.data(), dbits, (size_t)n, hipMemcpyDeviceToHost, s));
+    if (ransac_mask) SLAM_HIP(c, d.download(ransac_mask, s_mask, s));
+    SLAM_HIP(c, d.download(bits.data(), s_bits, s));
     SLAM_HIP(c, hipStreamSynchronize(s));
     int good[4] = {0, 0, 0, 0};
     for (int i = 0; i < n; i++)

@@ -173,18 +173,20 @@ int triangulate(slam_ctx* c, const double* K, const double* R1, const double* t1
     TriParams p;
     projection(K, R1, t1, p.P1);
     projection(K, R2, t2, p.P2);
-    const size_t pb = (size_t)n * sizeof(float2), ob = (size_t)n * 3 * sizeof(double);
-    SLAM_HIP(c, c->geom.ensure(2 * pb + ob + 256));
-    char* base = c->geom.as<char>();
-    float2* d1 = reinterpret_cast<float2*>(base);
-    float2* d2 = reinterpret_cast<float2*>(base + pb);
-    double* dout = reinterpret_cast<double*>(base + ((2 * pb + 255) & ~(size_t)255));
-    SLAM_HIP(c, hipMemcpyAsync(d1, pts1, pb, hipMemcpyHostToDevice, s));
-    SLAM_HIP(c, hipMemcpyAsync(d2, pts2, pb, hipMemcpyHostToDevice, s));
-    p.pts1 = d1; p.pts2 = d2; p.n = n; p.out = dout;
+    DevLayout lay;
+    const auto s1 = lay.add<float>(2 * (size_t)n), s2 = lay.add<float>(2 * (size_t)n);
+    const auto s_out = lay.add<double>(3 * (size_t)n);
+    DevMem d;
+    SLAM_HIP(c, d.bind(c->geom, lay));
+    SLAM_HIP(c, d.upload(s1, pts1, s));
+    SLAM_HIP(c, d.upload(s2, pts2, s));
+    p.pts1 = reinterpret_cast<const float2*>(d.ptr(s1));
+    p.pts2 = reinterpret_cast<const float2*>(d.ptr(s2));
+    p.n = n;
+    p.out = d.ptr(s_out);
     hipLaunchKernelGGL(tri_dlt, dim3((n + 127) / 128), dim3(128), 0, s, p);
     SLAM_HIP(c, hipGetLastError());
-    SLAM_HIP(c, hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, s));
+    SLAM_HIP(c, d.download(out, s_out, s));
     SLAM_HIP(c, hipStreamSynchronize(s));
     return SLAM_OK;
 }

@@ -522,19 +522,22 @@ extern "C" int slam_jpeg_encode(slam_ctx* c, const uint8_t* img, int h, int w, i
     if (int rc = jpeg::enc_setup(h, w, channels, row_step, 0, quality, sampling, restart_interval, g, T, msg))
         return set_err(c, rc, msg);
     SLAM_HIP(c, hipSetDevice(c->device));
-    const size_t row = (size_t)w * channels, o_out = align_up(row * h, 256), o_meta = o_out + align_up(cap, 256);
-    SLAM_HIP(c, c->jenc_io.ensure(o_meta + 256));
-    uint8_t* io = c->jenc_io.as<uint8_t>();
-    SLAM_HIP(c, hipMemcpy2D(io, row, img, row_step, row, h, hipMemcpyHostToDevice));
+    const size_t row = (size_t)w * channels;
+    DevLayout lay;
+    const auto s_img = lay.add<uint8_t>(row * h), s_out = lay.add<uint8_t>(cap);
+    const auto s_meta = lay.add<uint64_t>(2);       // the size, then the status in the second word's low half
+    DevMem io;
+    SLAM_HIP(c, io.bind(c->jenc_io, lay));
+    SLAM_HIP(c, hipMemcpy2D(io.ptr(s_img), row, img, row_step, row, h, hipMemcpyHostToDevice));
     g.row_step = row;
     g.frame_step = row * h;
-    uint64_t* d_size = reinterpret_cast<uint64_t*>(io + o_meta);
-    int32_t* d_stat = reinterpret_cast<int32_t*>(io + o_meta + 8);
-    if (int rc = encode_batch(c, c->stream, io, 1, g, T, restart_interval, io + o_out, cap, d_size, d_stat)) return rc;
+    uint64_t* d_size = io.ptr(s_meta);
+    int32_t* d_stat = reinterpret_cast<int32_t*>(d_size + 1);
+    if (int rc = encode_batch(c, c->stream, io.ptr(s_img), 1, g, T, restart_interval, io.ptr(s_out), cap, d_size, d_stat)) return rc;
     uint64_t meta[2] = {0, 0};
-    SLAM_HIP(c, hipMemcpy(meta, d_size, 16, hipMemcpyDeviceToHost));
+    SLAM_HIP(c, hipMemcpy(meta, d_size, s_meta.bytes(), hipMemcpyDeviceToHost));
     const size_t have = meta[0] < cap ? (size_t)meta[0] : cap;
-    if (have) SLAM_HIP(c, hipMemcpy(out, io + o_out, have, hipMemcpyDeviceToHost));
+    if (have) SLAM_HIP(c, hipMemcpy(out, io.ptr(s_out), have, hipMemcpyDeviceToHost));
     *size = (size_t)meta[0];
     if (status) *status = (int)(int32_t)(meta[1] & 0xFFFFFFFFu);
     return SLAM_OK;

@@ -400,8 +400,6 @@ __global__ __launch_bounds__(256) void pgo_step(const double* S, const double* x
     for (int k = 0; k < 8; k++) St[8 * (size_t)a + k] = s[k];
 }
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 }  // namespace slamhip
@@ -425,18 +423,16 @@ extern "C" int slam_sim3_ransac_dev(slam_ctx* c, void* stream, const double* d_a
     const size_t LH = (size_t)L * H;
     std::vector<int32_t> samples(3 * LH);
     loop_draw_samples(offsets, L, H, seed, samples.data());
-    // hypotheses and centres (f64) first, then the samples, the counts and the offsets
-    const size_t o_cen = 8 * 8 * LH, o_smp = o_cen + 8 * 6 * (size_t)L, o_cnt = o_smp + 4 * 3 * LH, o_off = o_cnt + 4 * LH;
-    SLAM_HIP(c, c->loop_ws.ensure(o_off + 4 * ((size_t)L + 1)));
-    uint8_t* w = c->loop_ws.as<uint8_t>();
-    double* hyp = reinterpret_cast<double*>(w);
-    double* cen = reinterpret_cast<double*>(w + o_cen);
-    int32_t* smp = reinterpret_cast<int32_t*>(w + o_smp);
-    int32_t* cnt = reinterpret_cast<int32_t*>(w + o_cnt);
-    int32_t* off = reinterpret_cast<int32_t*>(w + o_off);
-    SLAM_HIP(c, hipMemcpyAsync(cen, centres, 8 * 6 * (size_t)L, hipMemcpyHostToDevice, s));
-    SLAM_HIP(c, hipMemcpyAsync(smp, samples.data(), 4 * 3 * LH, hipMemcpyHostToDevice, s));
-    SLAM_HIP(c, hipMemcpyAsync(off, offsets, 4 * ((size_t)L + 1), hipMemcpyHostToDevice, s));
+    DevLayout lay;
+    const auto s_hyp = lay.add<double>(8 * LH), s_cen = lay.add<double>(6 * (size_t)L);
+    const auto s_smp = lay.add<int32_t>(3 * LH), s_cnt = lay.add<int32_t>(LH), s_off = lay.add<int32_t>((size_t)L + 1);
+    DevMem w;
+    SLAM_HIP(c, w.bind(c->loop_ws, lay));
+    double *hyp = w.ptr(s_hyp), *cen = w.ptr(s_cen);
+    int32_t *smp = w.ptr(s_smp), *cnt = w.ptr(s_cnt), *off = w.ptr(s_off);
+    SLAM_HIP(c, w.upload(s_cen, centres, s));
+    SLAM_HIP(c, w.upload(s_smp, samples.data(), s));
+    SLAM_HIP(c, w.upload(s_off, offsets, s));
     const double tau2 = tau * tau;
     hipLaunchKernelGGL(sim3_hyp, dim3((unsigned)((LH + 255) / 256)), dim3(256), 0, s, d_a, d_b, off, L, H, smp, hyp);
     hipLaunchKernelGGL(sim3_score, dim3((H + kScoreTile - 1) / kScoreTile, L), dim3(kScoreTile), 0, s, d_a, d_b, off, cen, H,
@@ -457,15 +453,16 @@ extern "C" int slam_sim3_apply_points_dev(slam_ctx* c, void* stream, const doubl
     if (!d_points || !d_anchor || !d_out) return set_err(c, SLAM_E_INVALID_ARG, "sim3 apply points: null argument");
     SLAM_HIP(c, hipSetDevice(c->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-    const size_t nb = 8 * 8 * (size_t)m;
-    SLAM_HIP(c, c->loop_ws.ensure(2 * nb + 8));
-    double* dn = c->loop_ws.as<double>();
+    DevLayout lay;
+    const auto s_old = lay.add<double>(8 * (size_t)m), s_new = lay.add<double>(8 * (size_t)m);
+    DevMem w;
+    SLAM_HIP(c, w.bind(c->loop_ws, lay));
     if (m > 0) {
-        SLAM_HIP(c, hipMemcpyAsync(dn, nodes, nb, hipMemcpyHostToDevice, s));
-        SLAM_HIP(c, hipMemcpyAsync(dn + 8 * (size_t)m, nodes_new, nb, hipMemcpyHostToDevice, s));
+        SLAM_HIP(c, w.upload(s_old, nodes, s));
+        SLAM_HIP(c, w.upload(s_new, nodes_new, s));
     }
-    hipLaunchKernelGGL(sim3_apply_points, dim3((n + 255) / 256), dim3(256), 0, s, d_points, d_anchor, n, dn, dn + 8 * (size_t)m, m,
-                       d_out);
+    hipLaunchKernelGGL(sim3_apply_points, dim3((n + 255) / 256), dim3(256), 0, s, d_points, d_anchor, n, w.ptr(s_old), w.ptr(s_new),
+                       m, d_out);
     SLAM_HIP(c, hipGetLastError());
     return stream_sync(c, s);
 }
@@ -491,32 +488,36 @@ extern "C" int slam_pgo_sim3_dev(slam_ctx* c, void* stream, double* d_nodes, int
     std::vector<double> zs(9 * (size_t)E);
     pgo_edge_constants(meas, weight, E, zs.data(), zs.data() + 8 * (size_t)E);
     const size_t N = 7 * (size_t)n, nE = (size_t)E;
-    // f64: S, St, zinv + sw, two linearisations (r, J, c), H, g, Hd, L, x, r, z, p, Ap, u, the scalars; then the ints
+    // a linearisation is r (7 E), J (98 E), c (E); zinv (8 E) and sw (E) share a slot, as the host's zs holds them
     const size_t lin = 7 * nE + 98 * nE + nE;
-    const size_t nd = 16 * (size_t)n + 9 * nE + 2 * lin + 3 * 49 * (size_t)n + 6 * N + 14 * nE + 8;
-    const size_t ni = 2 * nE + ((size_t)n + 1) + 2 * nE;
-    SLAM_HIP(c, c->loop_pgo.ensure(8 * nd + 4 * ni));
-    double* w = c->loop_pgo.as<double>();
-    double *S = w, *St = S + 8 * (size_t)n, *zinv = St + 8 * (size_t)n, *sw = zinv + 8 * nE, *linA = sw + nE, *linB = linA + lin;
-    double *H = linB + lin, *Hd = H + 49 * (size_t)n, *Lm = Hd + 49 * (size_t)n, *g = Lm + 49 * (size_t)n;
-    double *x = g + N, *r = x + N, *z = r + N, *p = z + N, *Ap = p + N, *u = Ap + N;
-    PgoSc* sc = reinterpret_cast<PgoSc*>(u + 14 * nE);
-    static_assert(sizeof(PgoSc) <= 8 * 8, "the scalars fit their slot");
-    int32_t* d_edges = reinterpret_cast<int32_t*>(w + nd);
-    int32_t *d_start = d_edges + 2 * nE, *d_ent = d_start + n + 1;
+    DevLayout lay;
+    const auto s_S = lay.add<double>(8 * (size_t)n), s_St = lay.add<double>(8 * (size_t)n), s_zs = lay.add<double>(9 * nE);
+    const auto s_linA = lay.add<double>(lin), s_linB = lay.add<double>(lin);
+    const auto s_H = lay.add<double>(49 * (size_t)n), s_Hd = lay.add<double>(49 * (size_t)n), s_Lm = lay.add<double>(49 * (size_t)n);
+    const auto s_g = lay.add<double>(N), s_x = lay.add<double>(N), s_r = lay.add<double>(N), s_z = lay.add<double>(N);
+    const auto s_p = lay.add<double>(N), s_Ap = lay.add<double>(N), s_u = lay.add<double>(14 * nE);
+    const auto s_sc = lay.add<PgoSc>(1);
+    const auto s_edges = lay.add<int32_t>(2 * nE), s_start = lay.add<int32_t>((size_t)n + 1), s_ent = lay.add<int32_t>(2 * nE);
+    DevMem w;
+    SLAM_HIP(c, w.bind(c->loop_pgo, lay));
+    double *S = w.ptr(s_S), *St = w.ptr(s_St), *zinv = w.ptr(s_zs), *sw = zinv + 8 * nE, *linA = w.ptr(s_linA), *linB = w.ptr(s_linB);
+    double *H = w.ptr(s_H), *Hd = w.ptr(s_Hd), *Lm = w.ptr(s_Lm), *g = w.ptr(s_g);
+    double *x = w.ptr(s_x), *r = w.ptr(s_r), *z = w.ptr(s_z), *p = w.ptr(s_p), *Ap = w.ptr(s_Ap), *u = w.ptr(s_u);
+    PgoSc* sc = w.ptr(s_sc);
+    int32_t *d_edges = w.ptr(s_edges), *d_start = w.ptr(s_start), *d_ent = w.ptr(s_ent);
     PgoSc* h_sc = static_cast<PgoSc*>(readback(c, sizeof(PgoSc)));
     if (!h_sc) return set_err(c, SLAM_E_HIP, "pgo sim3: no pinned readback space");
 
     SLAM_HIP(c, hipMemcpyAsync(S, d_nodes, 8 * 8 * (size_t)n, hipMemcpyDeviceToDevice, s));
     if (E > 0) {
-        SLAM_HIP(c, hipMemcpyAsync(zinv, zs.data(), 8 * 9 * nE, hipMemcpyHostToDevice, s));
-        SLAM_HIP(c, hipMemcpyAsync(d_edges, edges, 4 * 2 * nE, hipMemcpyHostToDevice, s));
-        SLAM_HIP(c, hipMemcpyAsync(d_ent, ent.data(), 4 * 2 * nE, hipMemcpyHostToDevice, s));
+        SLAM_HIP(c, w.upload(s_zs, zs.data(), s));
+        SLAM_HIP(c, w.upload(s_edges, edges, s));
+        SLAM_HIP(c, w.upload(s_ent, ent.data(), s));
     }
-    SLAM_HIP(c, hipMemcpyAsync(d_start, start.data(), 4 * ((size_t)n + 1), hipMemcpyHostToDevice, s));
+    SLAM_HIP(c, w.upload(s_start, start.data(), s));
     PgoSc init = {};
     init.tol = pcg_tol;
-    SLAM_HIP(c, hipMemcpyAsync(sc, &init, sizeof(PgoSc), hipMemcpyHostToDevice, s));
+    SLAM_HIP(c, w.upload(s_sc, &init, s));
     if (int rc = stream_sync(c, s)) return rc;      // the host vectors and `init` are free from here
 
     const unsigned gE = (unsigned)((E + 63) / 64), gN7 = (unsigned)((N + 255) / 256), gN = (unsigned)((n + 63) / 64);
@@ -591,13 +592,15 @@ extern "C" int slam_pgo_sim3(slam_ctx* c, double* nodes, int n, const int32_t* e
     if (loop_check_pgo(nodes, n, edges, meas, weight, E, ell, lambda0, max_lm, max_pcg, pcg_tol, cost_tol) || !cost || !iters)
         return set_err(c, SLAM_E_INVALID_ARG, "pgo sim3: bad arguments");
     SLAM_HIP(c, hipSetDevice(c->device));
-    SLAM_HIP(c, c->loop_in.ensure(8 * 8 * (size_t)n));
-    double* d = c->loop_in.as<double>();
-    SLAM_HIP(c, hipMemcpyAsync(d, nodes, 8 * 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    if (int rc = slam_pgo_sim3_dev(c, c->stream, d, n, edges, meas, weight, E, ell, lambda0, max_lm, max_pcg, pcg_tol, cost_tol,
-                                   cost, iters))
+    DevLayout lay;
+    const auto s_nodes = lay.add<double>(8 * (size_t)n);
+    DevMem d;
+    SLAM_HIP(c, d.bind(c->loop_in, lay));
+    SLAM_HIP(c, d.upload(s_nodes, nodes, c->stream));
+    if (int rc = slam_pgo_sim3_dev(c, c->stream, d.ptr(s_nodes), n, edges, meas, weight, E, ell, lambda0, max_lm, max_pcg, pcg_tol,
+                                   cost_tol, cost, iters))
         return rc;
-    SLAM_HIP(c, hipMemcpyAsync(nodes, d, 8 * 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    SLAM_HIP(c, d.download(nodes, s_nodes, c->stream));
     return stream_sync(c, c->stream);
 }
 
@@ -615,24 +618,25 @@ extern "C" int slam_sim3_ransac(slam_ctx* c, const double* a, const double* b, c
     SLAM_HIP(c, hipSetDevice(c->device));
     std::vector<int32_t> off((size_t)L + 1);
     for (int i = 0; i <= L; i++) off[i] = offsets[i] - p0;
-    const size_t pb = 8 * 3 * (size_t)(np > 0 ? np : 1);
-    const size_t o_b = up256(pb), o_sim = o_b + up256(pb), o_cnt = o_sim + up256(8 * 8 * (size_t)L);
-    const size_t o_st = o_cnt + up256(4 * (size_t)L), o_mask = o_st + up256(4 * (size_t)L);
-    SLAM_HIP(c, c->loop_in.ensure(o_mask + (size_t)(np > 0 ? np : 1)));
-    uint8_t* d = c->loop_in.as<uint8_t>();
+    DevLayout lay;
+    const auto s_a = lay.add<double>(3 * (size_t)np), s_b = lay.add<double>(3 * (size_t)np);
+    const auto s_sim = lay.add<double>(8 * (size_t)L);
+    const auto s_cnt = lay.add<int32_t>((size_t)L), s_st = lay.add<int32_t>((size_t)L);
+    const auto s_mask = lay.add<uint8_t>((size_t)np);
+    DevMem d;
+    SLAM_HIP(c, d.bind(c->loop_in, lay));
     hipStream_t s = c->stream;
     if (np > 0) {
-        SLAM_HIP(c, hipMemcpyAsync(d, a + 3 * (size_t)p0, 8 * 3 * (size_t)np, hipMemcpyHostToDevice, s));
-        SLAM_HIP(c, hipMemcpyAsync(d + o_b, b + 3 * (size_t)p0, 8 * 3 * (size_t)np, hipMemcpyHostToDevice, s));
+        SLAM_HIP(c, d.upload(s_a, a + 3 * (size_t)p0, s));
+        SLAM_HIP(c, d.upload(s_b, b + 3 * (size_t)p0, s));
     }
-    if (int rc = slam_sim3_ransac_dev(c, s, reinterpret_cast<double*>(d), reinterpret_cast<double*>(d + o_b), off.data(), L, centres,
-                                      H, tau, seed, reinterpret_cast<double*>(d + o_sim), d + o_mask,
-                                      reinterpret_cast<int32_t*>(d + o_cnt), reinterpret_cast<int32_t*>(d + o_st)))
+    if (int rc = slam_sim3_ransac_dev(c, s, d.ptr(s_a), d.ptr(s_b), off.data(), L, centres, H, tau, seed, d.ptr(s_sim), d.ptr(s_mask),
+                                      d.ptr(s_cnt), d.ptr(s_st)))
         return rc;
-    SLAM_HIP(c, hipMemcpyAsync(sim, d + o_sim, 8 * 8 * (size_t)L, hipMemcpyDeviceToHost, s));
-    SLAM_HIP(c, hipMemcpyAsync(count, d + o_cnt, 4 * (size_t)L, hipMemcpyDeviceToHost, s));
-    SLAM_HIP(c, hipMemcpyAsync(status, d + o_st, 4 * (size_t)L, hipMemcpyDeviceToHost, s));
-    if (np > 0) SLAM_HIP(c, hipMemcpyAsync(mask + p0, d + o_mask, (size_t)np, hipMemcpyDeviceToHost, s));
+    SLAM_HIP(c, d.download(sim, s_sim, s));
+    SLAM_HIP(c, d.download(count, s_cnt, s));
+    SLAM_HIP(c, d.download(status, s_st, s));
+    if (np > 0) SLAM_HIP(c, d.download(mask + p0, s_mask, s));
     return stream_sync(c, s);
 }
 
@@ -647,15 +651,15 @@ extern "C" int slam_sim3_apply_points(slam_ctx* c, const double* points, const i
     for (int i = 0; i < n; i++)
         if (anchor[i] < -1 || anchor[i] >= m) return set_err(c, SLAM_E_INVALID_ARG, "sim3 apply points: anchor outside [-1, m)");
     SLAM_HIP(c, hipSetDevice(c->device));
-    const size_t pb = 8 * 3 * (size_t)n, o_out = up256(pb), o_an = o_out + up256(pb);
-    SLAM_HIP(c, c->loop_in.ensure(o_an + 4 * (size_t)n));
-    uint8_t* d = c->loop_in.as<uint8_t>();
+    DevLayout lay;
+    const auto s_pts = lay.add<double>(3 * (size_t)n), s_out = lay.add<double>(3 * (size_t)n);
+    const auto s_an = lay.add<int32_t>((size_t)n);
+    DevMem d;
+    SLAM_HIP(c, d.bind(c->loop_in, lay));
     hipStream_t s = c->stream;
-    SLAM_HIP(c, hipMemcpyAsync(d, points, pb, hipMemcpyHostToDevice, s));
-    SLAM_HIP(c, hipMemcpyAsync(d + o_an, anchor, 4 * (size_t)n, hipMemcpyHostToDevice, s));
-    if (int rc = slam_sim3_apply_points_dev(c, s, reinterpret_cast<double*>(d), reinterpret_cast<int32_t*>(d + o_an), n, nodes,
-                                            nodes_new, m, reinterpret_cast<double*>(d + o_out)))
-        return rc;
-    SLAM_HIP(c, hipMemcpyAsync(out, d + o_out, pb, hipMemcpyDeviceToHost, s));
+    SLAM_HIP(c, d.upload(s_pts, points, s));
+    SLAM_HIP(c, d.upload(s_an, anchor, s));
+    if (int rc = slam_sim3_apply_points_dev(c, s, d.ptr(s_pts), d.ptr(s_an), n, nodes, nodes_new, m, d.ptr(s_out))) return rc;
+    SLAM_HIP(c, d.download(out, s_out, s));
     return stream_sync(c, s);
 }

@@ -589,25 +589,27 @@ extern "C" int slam_mvs_depth(slam_ctx* c, const uint8_t* ref, const uint8_t* co
         if (!srcs[s]) return set_err(c, SLAM_E_INVALID_ARG, "mvs depth: null source");
     SLAM_HIP(c, hipSetDevice(c->device));
     const size_t row = (size_t)w * channels, fb = row * h, npx = (size_t)w * h;
-    const size_t o_out = ((size_t)(S + 1) * fb + 255) & ~(size_t)255;
-    SLAM_HIP(c, c->mvs_in.ensure(o_out + npx * 10));
-    uint8_t* d = c->mvs_in.as<uint8_t>();
+    DevLayout lay;
+    const auto s_frames = lay.add<uint8_t>((size_t)(S + 1) * fb);
+    const auto s_cost = lay.add<int32_t>(npx);
+    const auto s_inv = lay.add<float>(npx);
+    const auto s_plane = lay.add<int16_t>(npx);
+    DevMem m;
+    SLAM_HIP(c, m.bind(c->mvs_in, lay));
+    uint8_t* d = m.ptr(s_frames);
     for (int f = 0; f <= S; f++)
         SLAM_HIP(c, hipMemcpy2DAsync(d + f * fb, row, f == 0 ? ref : srcs[f - 1], step, row, h, hipMemcpyHostToDevice,
                                      c->stream));
-    int32_t* dcost = reinterpret_cast<int32_t*>(d + o_out);
-    float* dinv = reinterpret_cast<float*>(d + o_out + npx * 4);
-    int16_t* dplane = reinterpret_cast<int16_t*>(d + o_out + npx * 8);
     const int32_t ref_idx = 0, nsrc = S, src_idx[4] = {1, 2, 3, 4};
     double M4[36] = {0}, v4[12] = {0};
     memcpy(M4, M, sizeof(double) * 9 * S);
     memcpy(v4, v, sizeof(double) * 3 * S);
     if (int rc = slam_mvs_depth_batch_dev(c, c->stream, d, S + 1, w, h, channels, 1, &ref_idx, &nsrc, src_idx, M4, v4,
-                                          planes, D, radius, uniq, min_views, dplane, dcost, dinv))
+                                          planes, D, radius, uniq, min_views, m.ptr(s_plane), m.ptr(s_cost), m.ptr(s_inv)))
         return rc;
-    SLAM_HIP(c, hipMemcpyAsync(cost, dcost, npx * 4, hipMemcpyDeviceToHost, c->stream));
-    SLAM_HIP(c, hipMemcpyAsync(inv_depth, dinv, npx * 4, hipMemcpyDeviceToHost, c->stream));
-    SLAM_HIP(c, hipMemcpyAsync(plane, dplane, npx * 2, hipMemcpyDeviceToHost, c->stream));
+    SLAM_HIP(c, m.download(cost, s_cost, c->stream));
+    SLAM_HIP(c, m.download(inv_depth, s_inv, c->stream));
+    SLAM_HIP(c, m.download(plane, s_plane, c->stream));
     return stream_sync(c, c->stream);
 }
 
@@ -628,15 +630,18 @@ extern "C" int slam_mvs_fuse(slam_ctx* c, const uint8_t* const* frames, int w, i
         if (!frames[i]) return set_err(c, SLAM_E_INVALID_ARG, "mvs fuse: null frame");
     SLAM_HIP(c, hipSetDevice(c->device));
     const size_t row = (size_t)w * channels, fb = row * h, npx = (size_t)w * h;
-    const size_t o_inv = ((size_t)nmaps * fb + 255) & ~(size_t)255;
-    SLAM_HIP(c, c->mvs_in.ensure(o_inv + npx * 4 * nmaps));
-    uint8_t* d = c->mvs_in.as<uint8_t>();
+    DevLayout lay;
+    const auto s_frames = lay.add<uint8_t>((size_t)nmaps * fb);
+    const auto s_inv = lay.add<float>(npx * nmaps);
+    DevMem m;
+    SLAM_HIP(c, m.bind(c->mvs_in, lay));
+    uint8_t* d = m.ptr(s_frames);
     std::vector<int32_t> idx((size_t)nmaps);
     for (int i = 0; i < nmaps; i++) {
         idx[i] = i;
         SLAM_HIP(c, hipMemcpy2DAsync(d + i * fb, row, frames[i], step, row, h, hipMemcpyHostToDevice, c->stream));
     }
-    SLAM_HIP(c, hipMemcpyAsync(d + o_inv, inv_depth, npx * 4 * nmaps, hipMemcpyHostToDevice, c->stream));
-    return slam_mvs_fuse_dev(c, c->stream, d, nmaps, w, h, channels, nmaps, idx.data(), reinterpret_cast<float*>(d + o_inv),
+    SLAM_HIP(c, m.upload(s_inv, inv_depth, c->stream));
+    return slam_mvs_fuse_dev(c, c->stream, d, nmaps, w, h, channels, nmaps, idx.data(), m.ptr(s_inv),
                              nnbr, nbr_idx, M, v, B, cvec, eps, min_consistent, step_px, radius, points, colors, cap, n_out);
 }

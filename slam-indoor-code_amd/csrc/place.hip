@@ -743,15 +743,17 @@ extern "C" int slam_voc_assign(slam_ctx* c, const uint8_t* desc, int n, const ui
     if (!word || !dist) return set_err(c, SLAM_E_INVALID_ARG, "voc assign: null output");
     SLAM_HIP(c, hipSetDevice(c->device));
     const size_t B = voc_desc_bytes(kind);
-    const size_t o_cent = (n * B + 255) & ~(size_t)255, o_word = (o_cent + K * B + 255) & ~(size_t)255;
-    SLAM_HIP(c, c->place_in.ensure(o_word + sizeof(int32_t) * 2 * (size_t)n));
-    uint8_t* d = c->place_in.as<uint8_t>();
-    int32_t* d_word = reinterpret_cast<int32_t*>(d + o_word);
-    SLAM_HIP(c, hipMemcpyAsync(d, desc, n * B, hipMemcpyHostToDevice, c->stream));
-    SLAM_HIP(c, hipMemcpyAsync(d + o_cent, cent, K * B, hipMemcpyHostToDevice, c->stream));
-    if (int rc = slam_voc_assign_dev(c, c->stream, d, n, d + o_cent, K, kind, d_word, d_word + n)) return rc;
-    SLAM_HIP(c, hipMemcpyAsync(word, d_word, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SLAM_HIP(c, hipMemcpyAsync(dist, d_word + n, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    DevLayout lay;
+    const auto s_desc = lay.add<uint8_t>(n * B), s_cent = lay.add<uint8_t>(K * B);
+    const auto s_word = lay.add<int32_t>((size_t)n), s_dist = lay.add<int32_t>((size_t)n);
+    DevMem d;
+    SLAM_HIP(c, d.bind(c->place_in, lay));
+    SLAM_HIP(c, d.upload(s_desc, desc, c->stream));
+    SLAM_HIP(c, d.upload(s_cent, cent, c->stream));
+    if (int rc = slam_voc_assign_dev(c, c->stream, d.ptr(s_desc), n, d.ptr(s_cent), K, kind, d.ptr(s_word), d.ptr(s_dist)))
+        return rc;
+    SLAM_HIP(c, d.download(word, s_word, c->stream));
+    SLAM_HIP(c, d.download(dist, s_dist, c->stream));
     return stream_sync(c, c->stream);
 }
 
@@ -762,12 +764,13 @@ extern "C" int slam_voc_train(slam_ctx* c, const uint8_t* desc, int n, int K, in
     if (place_check_train(desc, n, K, iters, kind, cent, iters_run)) return set_err(c, SLAM_E_INVALID_ARG, "voc train: bad arguments");
     SLAM_HIP(c, hipSetDevice(c->device));
     const size_t B = voc_desc_bytes(kind);
-    const size_t o_cent = (n * B + 255) & ~(size_t)255;
-    SLAM_HIP(c, c->place_in.ensure(o_cent + K * B));
-    uint8_t* d = c->place_in.as<uint8_t>();
-    SLAM_HIP(c, hipMemcpyAsync(d, desc, n * B, hipMemcpyHostToDevice, c->stream));
-    if (int rc = slam_voc_train_dev(c, c->stream, d, n, K, iters, kind, d + o_cent, iters_run)) return rc;
-    SLAM_HIP(c, hipMemcpyAsync(cent, d + o_cent, K * B, hipMemcpyDeviceToHost, c->stream));
+    DevLayout lay;
+    const auto s_desc = lay.add<uint8_t>(n * B), s_cent = lay.add<uint8_t>(K * B);
+    DevMem d;
+    SLAM_HIP(c, d.bind(c->place_in, lay));
+    SLAM_HIP(c, d.upload(s_desc, desc, c->stream));
+    if (int rc = slam_voc_train_dev(c, c->stream, d.ptr(s_desc), n, K, iters, kind, d.ptr(s_cent), iters_run)) return rc;
+    SLAM_HIP(c, d.download(cent, s_cent, c->stream));
     return stream_sync(c, c->stream);
 }
 
@@ -784,17 +787,17 @@ extern "C" int slam_bow_vectors(slam_ctx* c, const int32_t* word, const int32_t*
     SLAM_HIP(c, hipSetDevice(c->device));
     std::vector<int32_t> off((size_t)m + 1);
     for (int i = 0; i <= m; i++) off[i] = offsets[i] - w0;
-    const size_t o_vec = (sizeof(int32_t) * (size_t)std::max(nw, 1) + 255) & ~(size_t)255;
-    const size_t o_tot = o_vec + sizeof(uint32_t) * (size_t)m * K;      // a multiple of 4; padded to 8 below
-    const size_t o_tot8 = (o_tot + 7) & ~(size_t)7;
-    SLAM_HIP(c, c->place_in.ensure(o_tot8 + sizeof(uint64_t) * (size_t)m));
-    uint8_t* d = c->place_in.as<uint8_t>();
-    if (nw > 0) SLAM_HIP(c, hipMemcpyAsync(d, word + w0, sizeof(int32_t) * (size_t)nw, hipMemcpyHostToDevice, c->stream));
-    if (int rc = slam_bow_vectors_dev(c, c->stream, reinterpret_cast<int32_t*>(d), off.data(), m, weights, K,
-                                      reinterpret_cast<uint32_t*>(d + o_vec), reinterpret_cast<uint64_t*>(d + o_tot8)))
+    DevLayout lay;
+    const auto s_word = lay.add<int32_t>((size_t)nw);
+    const auto s_vec = lay.add<uint32_t>((size_t)m * K);
+    const auto s_tot = lay.add<uint64_t>((size_t)m);
+    DevMem d;
+    SLAM_HIP(c, d.bind(c->place_in, lay));
+    if (nw > 0) SLAM_HIP(c, d.upload(s_word, word + w0, c->stream));
+    if (int rc = slam_bow_vectors_dev(c, c->stream, d.ptr(s_word), off.data(), m, weights, K, d.ptr(s_vec), d.ptr(s_tot)))
         return rc;
-    SLAM_HIP(c, hipMemcpyAsync(vec, d + o_vec, sizeof(uint32_t) * (size_t)m * K, hipMemcpyDeviceToHost, c->stream));
-    SLAM_HIP(c, hipMemcpyAsync(total, d + o_tot8, sizeof(uint64_t) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    SLAM_HIP(c, d.download(vec, s_vec, c->stream));
+    SLAM_HIP(c, d.download(total, s_tot, c->stream));
     return stream_sync(c, c->stream);
 }
 
@@ -808,26 +811,24 @@ extern "C" int slam_bow_query(slam_ctx* c, const uint32_t* q, const uint64_t* qt
     if (nq == 0) return SLAM_OK;
     if (!q || !qtotal || !idx || !score || (m > 0 && (!db || !dbtotal))) return set_err(c, SLAM_E_INVALID_ARG, "bow query: null argument");
     SLAM_HIP(c, hipSetDevice(c->device));
-    // u64 totals, f64 scores and results first (8-byte aligned), then the u32 vectors and the indices
-    const size_t o_qt = 0, o_bt = o_qt + 8 * (size_t)nq, o_sc = o_bt + 8 * (size_t)m, o_out = o_sc + 8 * (size_t)nq * m;
-    const size_t o_q = o_out + 8 * (size_t)nq * k, o_db = o_q + 4 * (size_t)nq * K, o_idx = o_db + 4 * (size_t)m * K;
-    SLAM_HIP(c, c->place_in.ensure(o_idx + 4 * (size_t)nq * k));
-    uint8_t* d = c->place_in.as<uint8_t>();
+    const size_t Q = (size_t)nq, M = (size_t)m;
+    DevLayout lay;
+    const auto s_qt = lay.add<uint64_t>(Q), s_bt = lay.add<uint64_t>(M);
+    const auto s_sc = lay.add<double>(Q * M), s_out = lay.add<double>(Q * k);
+    const auto s_q = lay.add<uint32_t>(Q * K), s_db = lay.add<uint32_t>(M * K);
+    const auto s_idx = lay.add<int32_t>(Q * k);
+    DevMem d;
+    SLAM_HIP(c, d.bind(c->place_in, lay));
     hipStream_t s = c->stream;
-    SLAM_HIP(c, hipMemcpyAsync(d + o_qt, qtotal, 8 * (size_t)nq, hipMemcpyHostToDevice, s));
-    SLAM_HIP(c, hipMemcpyAsync(d + o_q, q, 4 * (size_t)nq * K, hipMemcpyHostToDevice, s));
+    SLAM_HIP(c, d.upload(s_qt, qtotal, s));
+    SLAM_HIP(c, d.upload(s_q, q, s));
     if (m > 0) {
-        SLAM_HIP(c, hipMemcpyAsync(d + o_bt, dbtotal, 8 * (size_t)m, hipMemcpyHostToDevice, s));
-        SLAM_HIP(c, hipMemcpyAsync(d + o_db, db, 4 * (size_t)m * K, hipMemcpyHostToDevice, s));
+        SLAM_HIP(c, d.upload(s_bt, dbtotal, s));
+        SLAM_HIP(c, d.upload(s_db, db, s));
     }
-    if (int rc = slam_bow_score_dev(c, s, reinterpret_cast<uint32_t*>(d + o_q), reinterpret_cast<uint64_t*>(d + o_qt), nq,
-                                    reinterpret_cast<uint32_t*>(d + o_db), reinterpret_cast<uint64_t*>(d + o_bt), m, K,
-                                    reinterpret_cast<double*>(d + o_sc)))
-        return rc;
-    if (int rc = slam_bow_topk_dev(c, s, reinterpret_cast<double*>(d + o_sc), nq, m, first, last, k,
-                                   reinterpret_cast<int32_t*>(d + o_idx), reinterpret_cast<double*>(d + o_out)))
-        return rc;
-    SLAM_HIP(c, hipMemcpyAsync(idx, d + o_idx, 4 * (size_t)nq * k, hipMemcpyDeviceToHost, s));
-    SLAM_HIP(c, hipMemcpyAsync(score, d + o_out, 8 * (size_t)nq * k, hipMemcpyDeviceToHost, s));
+    if (int rc = slam_bow_score_dev(c, s, d.ptr(s_q), d.ptr(s_qt), nq, d.ptr(s_db), d.ptr(s_bt), m, K, d.ptr(s_sc))) return rc;
+    if (int rc = slam_bow_topk_dev(c, s, d.ptr(s_sc), nq, m, first, last, k, d.ptr(s_idx), d.ptr(s_out))) return rc;
+    SLAM_HIP(c, d.download(idx, s_idx, s));
+    SLAM_HIP(c, d.download(score, s_out, s));
     return stream_sync(c, s);
 }

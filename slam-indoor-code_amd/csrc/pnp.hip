@@ -1003,30 +1003,30 @@ int pnp_ransac(slam_ctx* c, const float* op, const float* ip, int n, const doubl
     std::vector<int> sub((size_t)5 * iters);
     if (n == 5) for (int k = 0; k < 5; k++) sub[k] = k;
     else ransac_subsets5(n, iters, sub.data());
-    size_t off = 0;
-    auto carve = [&](size_t b) { const size_t o = off; off += (b + 255) & ~(size_t)255; return o; };
-    const size_t o_op = carve(sizeof(float) * 3 * (size_t)n), o_ip = carve(sizeof(float) * 2 * (size_t)n),
-                 o_sub = carve(sizeof(int) * 5 * (size_t)iters), o_hyp = carve(sizeof(double) * kHyp * iters),
-                 o_mod = carve(sizeof(double) * 12 * (size_t)iters), o_cnt = carve(sizeof(int) * (size_t)iters),
-                 o_mask = carve((size_t)n), o_idx = carve(sizeof(int) * (size_t)n),
-                 o_err = carve(sizeof(double) * 2 * (size_t)n * kSpec), o_J = carve(sizeof(double) * 12 * (size_t)n * kSpec),
-                 o_red = carve(sizeof(double) * 28 * kSpec);
-    SLAM_HIP(c, c->geom.ensure(off));
-    char* base = c->geom.as<char>();
-    float* dop = reinterpret_cast<float*>(base + o_op);
-    float* dip = reinterpret_cast<float*>(base + o_ip);
-    SLAM_HIP(c, hipMemcpyAsync(dop, op, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, s));
-    SLAM_HIP(c, hipMemcpyAsync(dip, ip, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
-    SLAM_HIP(c, hipMemcpyAsync(base + o_sub, sub.data(), sizeof(int) * 5 * (size_t)iters, hipMemcpyHostToDevice, s));
+    DevLayout lay;
+    const auto s_op = lay.add<float>(3 * (size_t)n), s_ip = lay.add<float>(2 * (size_t)n);
+    const auto s_sub = lay.add<int>(5 * (size_t)iters);
+    const auto s_hyp = lay.add<double>((size_t)kHyp * iters), s_mod = lay.add<double>(12 * (size_t)iters);
+    const auto s_cnt = lay.add<int>((size_t)iters);
+    const auto s_mask = lay.add<uint8_t>((size_t)n);
+    const auto s_idx = lay.add<int>((size_t)n);
+    const auto s_err = lay.add<double>(2 * (size_t)n * kSpec), s_J = lay.add<double>(12 * (size_t)n * kSpec);
+    const auto s_red = lay.add<double>((size_t)28 * kSpec);
+    DevMem dm;
+    SLAM_HIP(c, dm.bind(c->geom, lay));
+    float *dop = dm.ptr(s_op), *dip = dm.ptr(s_ip);
+    SLAM_HIP(c, dm.upload(s_op, op, s));
+    SLAM_HIP(c, dm.upload(s_ip, ip, s));
+    SLAM_HIP(c, dm.upload(s_sub, sub.data(), s));
     HypParams hp;
     hp.op = dop; hp.ip = dip;
-    hp.subsets = reinterpret_cast<const int*>(base + o_sub);
+    hp.subsets = dm.ptr(s_sub);
     hp.fx = K[0]; hp.fy = K[4]; hp.cx = K[2]; hp.cy = K[5];
-    hp.out = reinterpret_cast<double*>(base + o_hyp);
+    hp.out = dm.ptr(s_hyp);
     hipLaunchKernelGGL(pnp_hyp, dim3(iters), dim3(256), 0, s, hp);
     SLAM_HIP(c, hipGetLastError());
     std::vector<double> hyp((size_t)kHyp * iters);
-    SLAM_HIP(c, hipMemcpyAsync(hyp.data(), hp.out, sizeof(double) * kHyp * iters, hipMemcpyDeviceToHost, s));
+    SLAM_HIP(c, dm.download(hyp.data(), s_hyp, s));
     SLAM_HIP(c, hipStreamSynchronize(s));
     // models [rvec | tvec] and the rotation projectPoints re-derives from rvec
     std::vector<double> rt((size_t)6 * iters), models((size_t)12 * iters);
@@ -1047,16 +1047,15 @@ int pnp_ransac(slam_ctx* c, const float* op, const float* ip, int n, const doubl
     }
     ScoreParams sp;
     sp.op = dop; sp.ip = dip; sp.n = n;
-    sp.models = reinterpret_cast<const double*>(base + o_mod);
+    sp.models = dm.ptr(s_mod);
     sp.fx = K[0]; sp.fy = K[4]; sp.cx = K[2]; sp.cy = K[5];
     sp.thr2 = (float)((double)reproj * (double)reproj);
-    sp.counts = reinterpret_cast<int*>(base + o_cnt);
-    SLAM_HIP(c, hipMemcpyAsync(base + o_mod, models.data(), sizeof(double) * 12 * (size_t)iters,
-                               hipMemcpyHostToDevice, s));
+    sp.counts = dm.ptr(s_cnt);
+    SLAM_HIP(c, dm.upload(s_mod, models.data(), s));
     hipLaunchKernelGGL(pnp_score, dim3(iters), dim3(256), 0, s, sp);
     SLAM_HIP(c, hipGetLastError());
     std::vector<int> cnt(iters);
-    SLAM_HIP(c, hipMemcpyAsync(cnt.data(), sp.counts, sizeof(int) * (size_t)iters, hipMemcpyDeviceToHost, s));
+    SLAM_HIP(c, dm.download(cnt.data(), s_cnt, s));
     SLAM_HIP(c, hipStreamSynchronize(s));
     // RANSACPointSetRegistrator::run replayed on the speculative counts
     int best = -1, niters = maxIters, maxGood = 0;
@@ -1073,20 +1072,18 @@ int pnp_ransac(slam_ctx* c, const float* op, const float* ip, int n, const doubl
         if (mask) std::memset(mask, 0, (size_t)n);
         return SLAM_OK;
     }
-    uint8_t* dmask = reinterpret_cast<uint8_t*>(base + o_mask);
-    hipLaunchKernelGGL(pnp_mask, dim3((n + 255) / 256), dim3(256), 0, s, sp,
-                       (const double*)(base + o_mod + sizeof(double) * 12 * (size_t)best), dmask);
+    hipLaunchKernelGGL(pnp_mask, dim3((n + 255) / 256), dim3(256), 0, s, sp, sp.models + 12 * (size_t)best, dm.ptr(s_mask));
     SLAM_HIP(c, hipGetLastError());
     std::vector<uint8_t> hm((size_t)n);
-    SLAM_HIP(c, hipMemcpyAsync(hm.data(), dmask, (size_t)n, hipMemcpyDeviceToHost, s));
+    SLAM_HIP(c, dm.download(hm.data(), s_mask, s));
     SLAM_HIP(c, hipStreamSynchronize(s));
     std::vector<int> idx;
     idx.reserve(maxGood);
     for (int i = 0; i < n; i++)
         if (hm[i]) idx.push_back(i);
     const int m = (int)idx.size();
-    int* didx = reinterpret_cast<int*>(base + o_idx);
-    SLAM_HIP(c, hipMemcpyAsync(didx, idx.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, s));
+    int* didx = dm.ptr(s_idx);
+    SLAM_HIP(c, dm.upload(s_idx, idx.data(), (size_t)m, s));
     // cvFindExtrinsicCameraParams2(useExtrinsicGuess = 1): CvLevMarq on the host.
     // Each LM iteration evaluates the step at the current damping and the next
     // kSpec - 1 dampings together, every candidate with its Jacobian (J'J, J'e,
@@ -1097,12 +1094,12 @@ int pnp_ransac(slam_ctx* c, const float* op, const float* ip, int n, const doubl
     EvalParams ev;
     ev.fx = K[0]; ev.fy = K[4]; ev.cx = K[2]; ev.cy = K[5];
     ev.op = dop; ev.ip = dip; ev.idx = didx; ev.m = m;
-    ev.err = reinterpret_cast<double*>(base + o_err);
-    ev.J = reinterpret_cast<double*>(base + o_J);
+    ev.err = dm.ptr(s_err);
+    ev.J = dm.ptr(s_J);
     ev.err_stride = 2 * (size_t)m;
     ev.J_stride = 12 * (size_t)m;
     ev.withJ = 1;
-    double* dred = reinterpret_cast<double*>(base + o_red);
+    double* dred = dm.ptr(s_red);
     double* red = static_cast<double*>(readback(c, sizeof(double) * 28 * kSpec));   // pinned: async copy + polled sync
     if (!red) return set_err(c, SLAM_E_HIP, "pinned readback allocation failed");
     // evaluate nc parameter vectors (6 each) with their Jacobians: red[28 c + ...]
@@ -1119,7 +1116,7 @@ int pnp_ransac(slam_ctx* c, const float* op, const float* ip, int n, const doubl
                                m, 1, dred, ev.err_stride, ev.J_stride);
         }
         SLAM_HIP(c, hipGetLastError());
-        SLAM_HIP(c, hipMemcpyAsync(red, dred, sizeof(double) * 28 * nc, hipMemcpyDeviceToHost, s));
+        SLAM_HIP(c, dm.download(red, s_red, (size_t)28 * nc, s));
         n_evals++;
         return stream_sync(c, s, true);
     };

@@ -303,8 +303,6 @@ __global__ __launch_bounds__(256) void render_resolve(const uint64_t* __restrict
     if (depth) depth[(size_t)v * wh + pix] = d;
 }
 
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 bool render_args_ok(int n_pts, int n_faces, int n_lines, const void* pts, const void* colors, const void* faces, const void* lines,
                     const void* line_colors, const double* views, int nv, const double* cam, int w, int h, int point_size)
 {
@@ -333,24 +331,26 @@ int render_run(slam_ctx* c, hipStream_t s, const float* d_pts, const uint8_t* d_
     const int nchunks = (nv + chunk - 1) / chunk;
     const int mode = raster_mode == 3 ? 2 : raster_mode;
     const int cap = raster_mode == 3 ? kTinyPool : kLargePool;
-    const size_t o_counts = align256(sizeof(RenderHdr));
-    const size_t o_views = o_counts + align256(sizeof(unsigned long long));
-    const size_t o_items = o_views + align256((size_t)nv * 12 * sizeof(double));
-    const size_t o_keys = o_items + align256((size_t)kLargePool * sizeof(LargeItem));
-    SLAM_HIP(c, c->render_ws.ensure(o_keys + (size_t)chunk * wh * 8));
-    char* base = c->render_ws.as<char>();
-    RenderHdr* hdr = reinterpret_cast<RenderHdr*>(base);
-    unsigned long long* count = reinterpret_cast<unsigned long long*>(base + o_counts);
-    double* d_views = reinterpret_cast<double*>(base + o_views);
-    LargeItem* items = reinterpret_cast<LargeItem*>(base + o_items);
-    uint64_t* keys = reinterpret_cast<uint64_t*>(base + o_keys);
+    DevLayout lay;
+    const auto s_hdr = lay.add<RenderHdr>(1);     // first: slam_render_last_stats reads it at the buffer's start
+    const auto s_count = lay.add<unsigned long long>(1);
+    const auto s_views = lay.add<double>((size_t)nv * 12);
+    const auto s_items = lay.add<LargeItem>((size_t)kLargePool);
+    const auto s_keys = lay.add<uint64_t>((size_t)chunk * wh);
+    DevMem ws;
+    SLAM_HIP(c, ws.bind(c->render_ws, lay));
+    RenderHdr* hdr = ws.ptr(s_hdr);
+    unsigned long long* count = ws.ptr(s_count);
+    double* d_views = ws.ptr(s_views);
+    LargeItem* items = ws.ptr(s_items);
+    uint64_t* keys = ws.ptr(s_keys);
     // five events per chunk: the passes are timed without a host wait between chunks
     while (c->render_evs.size() < (size_t)nchunks * 5) {
         hipEvent_t e = nullptr;
         SLAM_HIP(c, hipEventCreate(&e));
         c->render_evs.push_back(e);
     }
-    SLAM_HIP(c, hipMemcpyAsync(d_views, views, (size_t)nv * 12 * sizeof(double), hipMemcpyHostToDevice, s));
+    SLAM_HIP(c, ws.upload(s_views, views, s));
 
     SLAM_HIP(c, hipMemsetAsync(hdr, 0, sizeof(RenderHdr), s));
     for (double& m : c->render_ms) m = 0;
@@ -438,32 +438,34 @@ int slam_render(slam_ctx* c, const float* pts, const uint8_t* colors, int n_pts,
     SLAM_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const size_t wh = (size_t)w * h;
-    const size_t o_col = align256((size_t)n_pts * 12), o_faces = o_col + align256((size_t)n_pts * 3);
-    const size_t o_lines = o_faces + align256((size_t)n_faces * 12), o_lcol = o_lines + align256((size_t)n_lines * 24);
-    const size_t in_bytes = o_lcol + align256((size_t)n_lines * 3);
-    const size_t o_ids = align256(wh * 3), o_depth = o_ids + wh * 4;
-    SLAM_HIP(c, c->render_in.ensure(std::max<size_t>(in_bytes, 256)));
-    SLAM_HIP(c, c->render_out.ensure(o_depth + wh * 4));
-    char* in = c->render_in.as<char>();
-    char* res = c->render_out.as<char>();
+    DevLayout lin, lout;
+    const auto s_pts = lin.add<float>((size_t)n_pts * 3);
+    const auto s_col = lin.add<uint8_t>((size_t)n_pts * 3);
+    const auto s_faces = lin.add<int32_t>((size_t)n_faces * 3);
+    const auto s_lines = lin.add<float>((size_t)n_lines * 6);
+    const auto s_lcol = lin.add<uint8_t>((size_t)n_lines * 3);
+    const auto s_out = lout.add<uint8_t>(wh * 3);
+    const auto s_ids = lout.add<int32_t>(wh);
+    const auto s_depth = lout.add<float>(wh);
+    DevMem in, res;
+    SLAM_HIP(c, in.bind(c->render_in, lin));
+    SLAM_HIP(c, res.bind(c->render_out, lout));
     if (n_pts) {
-        SLAM_HIP(c, hipMemcpyAsync(in, pts, (size_t)n_pts * 12, hipMemcpyHostToDevice, s));
-        SLAM_HIP(c, hipMemcpyAsync(in + o_col, colors, (size_t)n_pts * 3, hipMemcpyHostToDevice, s));
+        SLAM_HIP(c, in.upload(s_pts, pts, s));
+        SLAM_HIP(c, in.upload(s_col, colors, s));
     }
-    if (n_faces) SLAM_HIP(c, hipMemcpyAsync(in + o_faces, faces, (size_t)n_faces * 12, hipMemcpyHostToDevice, s));
+    if (n_faces) SLAM_HIP(c, in.upload(s_faces, faces, s));
     if (n_lines) {
-        SLAM_HIP(c, hipMemcpyAsync(in + o_lines, lines, (size_t)n_lines * 24, hipMemcpyHostToDevice, s));
-        SLAM_HIP(c, hipMemcpyAsync(in + o_lcol, line_colors, (size_t)n_lines * 3, hipMemcpyHostToDevice, s));
+        SLAM_HIP(c, in.upload(s_lines, lines, s));
+        SLAM_HIP(c, in.upload(s_lcol, line_colors, s));
     }
-    const int rc = render_run(c, s, reinterpret_cast<float*>(in), reinterpret_cast<uint8_t*>(in + o_col), n_pts,
-                              reinterpret_cast<int32_t*>(in + o_faces), n_faces, reinterpret_cast<float*>(in + o_lines),
-                              reinterpret_cast<uint8_t*>(in + o_lcol), n_lines, view, 1, cam, w, h, point_size,
-                              reinterpret_cast<uint8_t*>(res), ids ? reinterpret_cast<int32_t*>(res + o_ids) : nullptr,
-                              depth ? reinterpret_cast<float*>(res + o_depth) : nullptr, 0, 0);
+    const int rc = render_run(c, s, in.ptr(s_pts), in.ptr(s_col), n_pts, in.ptr(s_faces), n_faces, in.ptr(s_lines), in.ptr(s_lcol),
+                              n_lines, view, 1, cam, w, h, point_size, res.ptr(s_out), ids ? res.ptr(s_ids) : nullptr,
+                              depth ? res.ptr(s_depth) : nullptr, 0, 0);
     if (rc != SLAM_OK) return rc;
-    SLAM_HIP(c, hipMemcpyAsync(out, res, wh * 3, hipMemcpyDeviceToHost, s));
-    if (ids) SLAM_HIP(c, hipMemcpyAsync(ids, res + o_ids, wh * 4, hipMemcpyDeviceToHost, s));
-    if (depth) SLAM_HIP(c, hipMemcpyAsync(depth, res + o_depth, wh * 4, hipMemcpyDeviceToHost, s));
+    SLAM_HIP(c, res.download(out, s_out, s));
+    if (ids) SLAM_HIP(c, res.download(ids, s_ids, s));
+    if (depth) SLAM_HIP(c, res.download(depth, s_depth, s));
     SLAM_HIP(c, hipStreamSynchronize(s));
     return SLAM_OK;
 }

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/slamhip.h"
+#include "dev_layout.h"
 
 namespace slamhip {
 
@@ -154,6 +155,30 @@ struct DevBuf {
     hipError_t ensure(size_t n);
     void release();
     template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+// A finished DevLayout bound to a DevBuf.  bind() sizes the buffer once and may
+// move it, so slots become pointers only through a bound DevMem; the copies take
+// their byte count from the slot (count: a leading part of it).
+struct DevMem {
+    uint8_t* base = nullptr;
+    hipError_t bind(DevBuf& buf, const DevLayout& layout)
+    {
+        const hipError_t e = buf.ensure(layout.bytes());
+        base = e == hipSuccess ? buf.as<uint8_t>() : nullptr;
+        return e;
+    }
+    template <class T> T* ptr(Slot<T> s) const { return reinterpret_cast<T*>(base + s.off); }
+    template <class T> hipError_t upload(Slot<T> s, const T* host, hipStream_t st) const { return upload(s, host, s.count, st); }
+    template <class T> hipError_t upload(Slot<T> s, const T* host, size_t count, hipStream_t st) const
+    {
+        return count > s.count ? hipErrorInvalidValue : hipMemcpyAsync(ptr(s), host, count * sizeof(T), hipMemcpyHostToDevice, st);
+    }
+    template <class T> hipError_t download(T* host, Slot<T> s, hipStream_t st) const { return download(host, s, s.count, st); }
+    template <class T> hipError_t download(T* host, Slot<T> s, size_t count, hipStream_t st) const
+    {
+        return count > s.count ? hipErrorInvalidValue : hipMemcpyAsync(host, ptr(s), count * sizeof(T), hipMemcpyDeviceToHost, st);
+    }
 };
 
 // the gradient map's zero border as last written by sift_blur_grad: buffer

@@ -266,6 +266,31 @@ def test_views_chunks_and_repeats(gpu_ctx):
     assert len({together[0][i].tobytes() for i in range(3)}) == 3       # three different pictures
 
 
+@pytest.mark.parametrize("planes", ["ids_depth", "frame_only"])
+def test_host_buffers_tiny_odd_view(gpu_ctx, planes):
+    """slam_render (host buffers, one view) at 5 x 3 pixels with three vertices, one face and one line:
+    every staged array has an odd byte count; the reference's bits, and nothing past an output's end"""
+    cam, size = (4.0, 4.0, 2.5, 1.5, 0.5, 100.0), (5, 3)
+    pts = np.asarray([at(0.5, 0.5, 4.0, cam), at(4.5, 0.5, 4.0, cam), at(0.5, 2.5, 4.0, cam)], np.float32)
+    cols, faces = colours(3, 3), np.array([[0, 1, 2]], np.int32)
+    lines = np.asarray([at(0.5, 2.5, 3.0, cam) + at(4.5, 2.5, 3.0, cam)], np.float32)
+    lcols = colours(1, 4)
+    want = RR.render(pts, cols, faces, lines, lcols, V0, cam, size)
+    assert len(np.unique(kinds(want[1])[0])) > 2                     # the face, the line or a point, and background
+    wh, tail = 15, 64
+    out = np.full(wh * 3 + tail, 0xA5, np.uint8)
+    ids = np.full(wh + tail, -77, np.int32) if planes == "ids_depth" else None
+    depth = np.full(wh + tail, -77.0, np.float32) if planes == "ids_depth" else None
+    vw, cm = api._views(V0), np.ascontiguousarray(cam, np.float64)
+    h = gpu_ctx.handle
+    L.check(L.lib().slam_render(h, L.ptr(pts), L.ptr(cols), 3, L.ptr(faces), 1, L.ptr(lines), L.ptr(lcols), 1, L.ptr(vw),
+                                L.ptr(cm), 5, 3, 1, L.ptr(out), L.ptr(ids), L.ptr(depth)), h)
+    assert out[:wh * 3].tobytes() == want[0].tobytes() and (out[wh * 3:] == 0xA5).all()
+    if planes == "ids_depth":
+        assert ids[:wh].tobytes() == want[1].tobytes() and (ids[wh:] == -77).all()
+        assert depth[:wh].tobytes() == want[2].tobytes() and (depth[wh:] == -77.0).all()
+
+
 def test_resident_tensors(gpu_ctx):
     import torch
     pts, cols, faces, lines, lcols = small_scene(4)
