@@ -1328,6 +1328,51 @@ int slam_sim3_ransac_host(const double* a, const double* b, const int32_t* offse
 int slam_sim3_apply_points_host(const double* points, const int32_t* anchor, int n, const double* nodes,
                                 const double* nodes_new, int m, double* out);
 
+/* ---- global bundle adjustment after loop closing (csrc/gba.hip; the contract is tests/gba_ref.py) ----
+ * Minimises the reprojection error over all n cameras and m points with the intrinsics
+ * K4 = {fx, fy, cx, cy} (host) held constant.  A camera is 7 f64 (qw, qx, qy, qz, tx,
+ * ty, tz), X_c = R(q) X + t with q a unit quaternion; camera 0 is fixed.  Observation o
+ * is (obs_cam[o], obs_point[o], obs_xy[2 o], obs_xy[2 o + 1]), host arrays; its residual
+ * is pi(X_c) - xy.  Excluded at entry and for the whole solve: an observation with
+ * z_c <= zmin, then every observation of a point left with fewer than two; such a point
+ * keeps its bits, and a camera left with no observation is held like camera 0.  A trial
+ * step that brings a kept observation to z_c <= zmin is rejected.  Loss 0: squares;
+ * loss 1: Huber with parameter loss_param on s = |r|^2 (rho = s for s <= a^2, else
+ * 2 a sqrt(s) - a^2), entering as plain reweighting: r and J times sqrt(rho').
+ * Levenberg-Marquardt with slam_pgo_sim3's rule; each step solves the Schur complement
+ * onto the cameras by conjugate gradients without forming it (two passes over the
+ * observations per iteration), preconditioned by its 6 x 6 diagonal blocks, until
+ * r.z <= pcg_tol (r.z)_0 or max_pcg iterations; a point whose damped 3 x 3 block has no
+ * Cholesky factor is frozen for that step.  Sums run in the orders of tests/gba_ref.py.
+ * n <= 1 or no kept observation: SLAM_OK, nothing changes, both costs 0.
+ * SLAM_E_INVALID_ARG: an index out of range, a zero quaternion, fx or fy <= 0,
+ * zmin <= 0, a negative cap, tolerance or lambda0, an unknown loss, Huber with
+ * loss_param <= 0, a pixel that is not finite. */
+enum { SLAM_GBA_LOSS_SQUARE = 0, SLAM_GBA_LOSS_HUBER = 1 };
+typedef struct slam_gba_params {
+    int32_t loss;
+    double loss_param, zmin, lambda0;
+    int32_t max_lm, max_pcg;
+    double pcg_tol, cost_tol;
+} slam_gba_params;
+typedef struct slam_gba_summary {
+    double cost0, cost;          /* sum of rho over the kept observations, before and after */
+    int32_t lm_steps, accepted, pcg_iters;
+    int32_t kept_obs, behind_obs, points_held, cams_held;
+} slam_gba_summary;
+/* d_cams (n x 7) and d_points (m x 3) are device pointers, updated in place. */
+int slam_gba_dev(slam_ctx* ctx, void* stream, const double* K4, double* d_cams, int n, double* d_points, int m,
+                 const int32_t* obs_cam, const int32_t* obs_point, const double* obs_xy, int nobs,
+                 const slam_gba_params* prm, slam_gba_summary* out);
+/* The same with cameras and points in host memory. */
+int slam_gba(slam_ctx* ctx, const double* K4, double* cams, int n, double* points, int m, const int32_t* obs_cam,
+             const int32_t* obs_point, const double* obs_xy, int nobs, const slam_gba_params* prm,
+             slam_gba_summary* out);
+/* The host twin: no context, no device, the same arithmetic (csrc/gba_math.h), the same bits. */
+int slam_gba_host(const double* K4, double* cams, int n, double* points, int m, const int32_t* obs_cam,
+                  const int32_t* obs_point, const double* obs_xy, int nobs, const slam_gba_params* prm,
+                  slam_gba_summary* out);
+
 #ifdef __cplusplus
 }
 #endif

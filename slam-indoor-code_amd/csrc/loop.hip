@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "loop_math.h"
+#include "pcg_kernels.h"
 #include "slamhip_internal.h"
 
 namespace slamhip {
@@ -219,14 +220,9 @@ __global__ __launch_bounds__(256) void sim3_apply_points(const double* pts, cons
 //   pgo_damp       one thread per node: Hd = H + lambda diag(H) and its Cholesky factor
 //   pgo_edge_mul   one thread per (edge, side): u = J p
 //   pgo_apply      one thread per (node, row): Hd_aa p_a + sum J_a^T u_b over the same list
-//   pgo_reduce     one workgroup of 1024: the 1024 strided partial sums, the binary tree in LDS, and the
+//   pgo_reduce     (pcg_kernels.h, shared with gba.hip) one workgroup of 1024: the 1024 strided partial sums, the binary tree in LDS, and the
 //                  scalar work of its step (cost; rz0 and the start flag; alpha; beta, the count and the
 //                  stop flag).  Once the stop flag is set every kernel of the loop returns at once.
-struct PgoSc {
-    double rz, rz0, alpha, beta, cost, tol;
-    int done, iters;
-};
-
 __global__ __launch_bounds__(64) void pgo_linearize(const double* S, const int32_t* edges, const double* zinv,
                                                     const double* sw, int E, double ell, double* r, double* J, double* c)
 {
@@ -246,43 +242,6 @@ __global__ __launch_bounds__(64) void pgo_linearize(const double* S, const int32
         J[98 * (size_t)e + 49 + k] = Jj[k];
     }
     c[e] = pgo_edge_cost(rr);
-}
-
-__global__ __launch_bounds__(kPgoLanes) void pgo_reduce(const double* a, const double* b, size_t n, PgoSc* sc, int mode)
-{
-    __shared__ double part[kPgoLanes];
-    if (mode >= 2 && sc->done) return;      // uniform
-    const int t = threadIdx.x;
-    double acc = 0.0;
-    for (size_t i = t; i < n; i += kPgoLanes) acc = acc + (b ? a[i] * b[i] : a[i]);
-    part[t] = acc;
-    __syncthreads();
-    for (int off = kPgoLanes / 2; off >= 1; off >>= 1) {
-        if (t < off) part[t] = part[t] + part[t + off];
-        __syncthreads();
-    }
-    if (t != 0) return;
-    const double sum = part[0];
-    if (mode == 0) {
-        sc->cost = sum;
-    } else if (mode == 1) {
-        sc->rz = sum;
-        sc->rz0 = sum;
-        sc->done = sum > 0.0 ? 0 : 1;
-        sc->iters = 0;
-    } else if (mode == 2) {
-        if (!(sum > 0.0))
-            sc->done = 1;
-        else
-            sc->alpha = sc->rz / sum;
-    } else {
-        sc->iters = sc->iters + 1;
-        if (sum <= sc->tol * sc->rz0)
-            sc->done = 1;
-        else
-            sc->beta = sum / sc->rz;
-        sc->rz = sum;
-    }
 }
 
 __global__ __launch_bounds__(256) void pgo_assemble(const double* r, const double* J, const int32_t* start, const int32_t* ent,
@@ -379,14 +338,6 @@ __global__ __launch_bounds__(64) void pgo_update(const double* Lm, int n, const 
     }
     pgo_block_solve(Lm + 49 * (size_t)a, rr, zz);
     for (int k = 0; k < 7; k++) z[7 * (size_t)a + k] = zz[k];
-}
-
-__global__ __launch_bounds__(256) void pgo_pupdate(int N, const double* z, double* p, const PgoSc* sc)
-{
-    if (sc->done) return;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    p[i] = z[i] + sc->beta * p[i];
 }
 
 __global__ __launch_bounds__(256) void pgo_step(const double* S, const double* x, int n, double* St)

@@ -377,6 +377,8 @@ struct slam_ctx {
     // the two node lists of a point correction), the staged buffers of the host-pointer calls
     slamhip::DevBuf loop_ws, loop_in;
     slamhip::DevBuf loop_pgo;             // slam_pgo_sim3_dev: nodes, linearisations, blocks, PCG vectors, scalars, lists
+    // global bundle adjustment (gba.hip): the solver's working set, the staged cameras + points of slam_gba
+    slamhip::DevBuf gba_ws, gba_in;
 
     bool prof_on = false;
     slamhip::ProfFamily prof[slamhip::kProfFamilies];

@@ -40,6 +40,8 @@ from . import place
 from . import loopclose
 from .loopclose import (apply_points, close_loops, correct_map, loop_constraints, optimize_pose_graph,
                         sim3_from_pairs)
+from . import globalba
+from .globalba import global_bundle_adjust, merge_observations, refine_closed
 from .video import VideoCapture, VideoWriter, write_mjpeg_avi
 from .config import ConfigError, ConfigService, reference_example
 from .calibration import CalibrationError, chessboard_photos_calibration

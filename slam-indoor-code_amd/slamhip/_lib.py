@@ -50,6 +50,7 @@ JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = 0, 0x11, 0x21, 0x22      # slam_jpeg_i
 JPEG_EOF, JPEG_BAD_CODE, JPEG_RUN, JPEG_RESTART = 1, 2, 4, 8       # entropy fault bits of a decode's status
 JPEG_ENC_OVERFLOW, JPEG_ENC_CATEGORY = 1, 2                        # status bits of an encode
 SIM3_OK, SIM3_NO_MODEL, SIM3_TOO_FEW, SIM3_CHOLESKY = range(4)                      # slam_sim3_ransac's status
+GBA_LOSS_SQUARE, GBA_LOSS_HUBER = 0, 1                             # slam_gba_params.loss
 VOC_SIFT, VOC_ORB = 0, 1                                           # slam_voc_*'s descriptor kind
 RENDER_POINT, RENDER_LINE, RENDER_FACE = 0, 1, 2                   # the kind in a rendered id (kind << 30 | index)
 RENDER_AUTO, RENDER_THREAD, RENDER_WAVE, RENDER_WAVE_FULL_LIST = 0, 1, 2, 3   # slam_render_views_dev's raster_mode
@@ -88,6 +89,18 @@ class AviInfo(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("rate", ctypes.c_uint32),
                 ("scale", ctypes.c_uint32), ("frames", ctypes.c_int64), ("handler", ctypes.c_uint32),
                 ("compression", ctypes.c_uint32), ("stream", ctypes.c_int32)]
+
+
+class GbaParams(ctypes.Structure):
+    _fields_ = [("loss", ctypes.c_int32), ("loss_param", ctypes.c_double), ("zmin", ctypes.c_double),
+                ("lambda0", ctypes.c_double), ("max_lm", ctypes.c_int32), ("max_pcg", ctypes.c_int32),
+                ("pcg_tol", ctypes.c_double), ("cost_tol", ctypes.c_double)]
+
+
+class GbaSummary(ctypes.Structure):
+    _fields_ = [("cost0", ctypes.c_double), ("cost", ctypes.c_double), ("lm_steps", ctypes.c_int32),
+                ("accepted", ctypes.c_int32), ("pcg_iters", ctypes.c_int32), ("kept_obs", ctypes.c_int32),
+                ("behind_obs", ctypes.c_int32), ("points_held", ctypes.c_int32), ("cams_held", ctypes.c_int32)]
 
 
 # exported symbols and their signatures: (restype, argtypes)
@@ -240,6 +253,9 @@ SIGNATURES = {
     "slam_sim3_apply_points_dev": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _P]),
     "slam_sim3_apply_points": (_I, [_P, _P, _P, _I, _P, _P, _I, _P]),
     "slam_sim3_apply_points_host": (_I, [_P, _P, _I, _P, _P, _I, _P]),
+    "slam_gba_dev": (_I, [_P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P]),
+    "slam_gba": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P]),
+    "slam_gba_host": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P]),
 }
 
 _lib = None

@@ -1553,6 +1553,12 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
     colors_closed.txt are written in rawOutput's format.  Nothing is appended to the four
     result files or to loops.txt; with no accepted loop the closed files repeat the open
     ones.  Together with tracker="klt" or undistort="points" it raises ValueError.
+    loops.global_ba (opt-in, needs loops.close): globalba.refine_closed then re-fits the closed
+    cameras and points to the run's observations with K constant.  gd.refined holds the result
+    (rotations, motions, points, colors, summary) and gd.closed stays as it is; with out_dir,
+    poses_refined.txt, rotations_refined.txt, points_refined.txt and colors_refined.txt are
+    written.  With no accepted loop they repeat the closed files.  Without loops.close it
+    raises ValueError.
     Returns (GlobalData, Logs)."""
     if undistort not in ("frames", "points"):
         raise ValueError('undistort: "frames" or "points"')
@@ -1561,6 +1567,8 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
     if tracker is not None and dist is not None:
         raise ValueError("tracker together with dist is not supported")
     close = loops is not None and getattr(loops, "close", False)
+    if loops is not None and getattr(loops, "global_ba", False) and not close:
+        raise ValueError("loops.global_ba needs loops.close")
     if close and (tracker is not None or undistort == "points"):
         raise ValueError('loops.close together with tracker="klt" or undistort="points" is not supported')
     if _is_fisheye(lens_model) and (dist is None or np.size(dist) != 4):
@@ -1645,4 +1653,13 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
                     with open(os.path.join(logs.out_dir, name), "w") as f:
                         for r in rows:
                             raw_output(r, f)
+            if getattr(loops, "global_ba", False):
+                from .globalba import refine_closed
+                gd.refined = refine_closed(gd.closed, logs.obs, K, loops, ctx=getattr(ops, "ctx", None), host=not hasattr(ops, "ctx"))
+                if logs.out_dir:
+                    for name, rows in (("poses_refined.txt", gd.refined["motions"]), ("rotations_refined.txt", gd.refined["rotations"]),
+                                       ("points_refined.txt", gd.refined["points"]), ("colors_refined.txt", gd.refined["colors"])):
+                        with open(os.path.join(logs.out_dir, name), "w") as f:
+                            for r in rows:
+                                raw_output(r, f)
     return gd, logs

@@ -273,13 +273,10 @@ def anchors_of(obs, npoints):
     return anchor
 
 
-def correct_map(points, colors, obs, nodes, nodes_new, constraints, ctx=None, host=False):
-    """Moves every point with its anchor node (apply_points) and merges the duplicates that the accepted
-    loops' inlier pairs name: of each set the lowest index stays (with its colour), the others are dropped.
-    Returns (points, colors, dropped indices)."""
-    points = _f64(points, 3)
-    moved = apply_points(points, anchors_of(obs, len(points)), nodes, nodes_new, ctx=ctx, host=host)
-    parent = np.arange(len(points))
+def merged_roots(npoints, constraints):
+    """The representative of every point under the merges that the accepted loops' inlier pairs name (union-find,
+    the lowest index of a set is its root): root[i] == i for a point that stays."""
+    parent = np.arange(npoints)
 
     def find(x):
         while parent[x] != x:
@@ -293,8 +290,16 @@ def correct_map(points, colors, obs, nodes, nodes_new, constraints, ctx=None, ho
                 ra, rb = find(int(a)), find(int(b))
                 if ra != rb:
                     parent[max(ra, rb)] = min(ra, rb)
-    root = np.array([find(x) for x in range(len(points))], np.int64)
-    keep = root == np.arange(len(points))
+    return np.array([find(x) for x in range(npoints)], np.int64)
+
+
+def correct_map(points, colors, obs, nodes, nodes_new, constraints, ctx=None, host=False):
+    """Moves every point with its anchor node (apply_points) and merges the duplicates that the accepted
+    loops' inlier pairs name: of each set the lowest index stays (with its colour), the others are dropped.
+    Returns (points, colors, dropped indices)."""
+    points = _f64(points, 3)
+    moved = apply_points(points, anchors_of(obs, len(points)), nodes, nodes_new, ctx=ctx, host=host)
+    keep = merged_roots(len(points), constraints) == np.arange(len(points))
     colors = np.asarray(colors)
     return moved[keep], colors[keep] if len(colors) == len(points) else colors, np.flatnonzero(~keep)
 

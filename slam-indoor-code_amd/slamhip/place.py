@@ -460,7 +460,9 @@ class LoopParams:
     alpha), kept when verify_loop finds at least min_inliers.  close=True adds the loop-closing
     stage (loopclose.close_loops over the kept loops): `hypotheses` RANSAC hypotheses per loop,
     the angular inlier threshold `tau`, at least `min_pairs` pairs and inliers per accepted loop,
-    the optimiser's caps `max_lm` / `max_pcg` and the weight of a loop edge."""
+    the optimiser's caps `max_lm` / `max_pcg` and the weight of a loop edge.  global_ba=True (with close)
+    then re-fits the closed map to the pixels (globalba.refine_closed): the loss `gba_loss` (0 squares,
+    1 Huber with `gba_loss_param` pixels), the caps `gba_max_lm` / `gba_max_pcg`, the least depth `gba_zmin`."""
     K: int = 4096
     iters: int = 10
     gap: int = 10
@@ -475,6 +477,12 @@ class LoopParams:
     max_lm: int = 10
     max_pcg: int = 400
     loop_weight: float = 1.0
+    global_ba: bool = False
+    gba_loss: int = 0
+    gba_loss_param: float = 1.0
+    gba_max_lm: int = 10
+    gba_max_pcg: int = 200
+    gba_zmin: float = 0.1
 
 
 def find_loops(frames, K, cond, ops, prm, ctx=None, host=False):

@@ -69,11 +69,12 @@ def load_global_data(out_dir, cloud="sparse"):
     cloud="dense" reads dense_points.txt / dense_colors.txt (slam_main(dense=...))
     in place of the sparse cloud's files; cloud="closed" reads the four *_closed.txt
     files of slam_main(loops=LoopParams(close=True)): corrected cameras and the
-    merged cloud."""
-    if cloud not in ("sparse", "dense", "closed"):
-        raise ValueError('cloud: "sparse" or "dense" (or "closed")')
+    merged cloud; cloud="refined" reads the four *_refined.txt files that
+    global_ba=True adds: the closed map after global bundle adjustment."""
+    if cloud not in ("sparse", "dense", "closed", "refined"):
+        raise ValueError('cloud: "sparse" or "dense" (or "closed", "refined")')
     prefix = "dense_" if cloud == "dense" else ""
-    suffix = "_closed" if cloud == "closed" else ""
+    suffix = "_" + cloud if cloud in ("closed", "refined") else ""
     poses = _rows(os.path.join(out_dir, "poses" + suffix + ".txt"), 3)
     rotations = _rows(os.path.join(out_dir, "rotations" + suffix + ".txt"), 9)
     if len(rotations) != len(poses):
@@ -353,7 +354,8 @@ def main(config_path, render=None, cloud="sparse"):
     reference view, and render = ("fly.avi", keys) encodes those frames where they
     were rendered and writes one Motion-JPEG AVI.  The default writes nothing more.
     cloud="dense" works on the dense cloud of slam_main(dense=...) instead, cloud="closed"
-    on the corrected cameras and merged cloud of slam_main(loops=LoopParams(close=True))."""
+    on the corrected cameras and merged cloud of slam_main(loops=LoopParams(close=True)),
+    cloud="refined" on that map after global bundle adjustment (global_ba=True)."""
     cfg = ConfigService()
     cfg.setConfigFile(config_path)
     if not cfg.getValue("onlyViz"):
