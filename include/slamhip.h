@@ -1192,6 +1192,83 @@ int slam_mvs_depth_host(const uint8_t* ref, const uint8_t* const* srcs, int S, i
                         const double* M, const double* v, const double* planes, int D, int radius, int uniq,
                         int min_views, int16_t* plane, int32_t* cost, float* inv_depth);
 
+/* ---- surface from the depth maps: TSDF fusion and marching cubes (tsdf.hip) -------- */
+/* An opt-in stage after the depth maps.  The definition of
+ * every value is tests/tsdf_ref.py; the device and the host twins equal it bit for
+ * bit.  The reference has no such stage.
+ *
+ * The volume: a grid of nx x ny x nz nodes, each dimension in 2..2048 and nx ny nz
+ * <= 2^30 (else SLAM_E_UNSUPPORTED); node (i, j, k) sits at X = origin[0] +
+ * (double)i voxel, Y and Z likewise.  Its state is six int32 planes [6][nz][ny][nx]
+ * (x fastest) D, W, CW, B, G, R owned by the caller; all zeros is the empty volume.
+ * Every sum is an integer, so the volume after a set of maps does not depend on
+ * their order or on how they are split over calls.  A volume takes at most 2^20
+ * maps in total (the caller counts); a call takes at most 2^20.
+ *
+ * slam_tsdf_integrate_dev adds nmaps depth maps (d_inv_depth: nmaps x h x w f32,
+ * device; map m belongs to frame frame_idx[m] of the nframes resident frames, m
+ * itself when frame_idx is NULL) with the projections P (host, nmaps x 12, row-
+ * major 3 x 4, mathematically K [R | t]; the library never forms one).  Per node
+ * and map, in f64 in this order without contraction:
+ *   h_i = ((P[i][0] X + P[i][1] Y) + P[i][2] Z) + P[i][3],  u = h_0 / h_2,  v = h_1 / h_2,
+ * valid iff h_2 > 0, -0.5 <= u < W - 0.5 and -0.5 <= v < H - 0.5 (a NaN or an
+ * infinity is invalid), then ix = (int)floor(u + 0.5), iy likewise; w =
+ * inv_depth[iy][ix], skipped unless w > 0; r = (1.0 / (double)w - h_2) / trunc,
+ * skipped when r < -1.0 (hidden behind the surface), r = 1.0 when r > 1.0; D +=
+ * (int32)floor(r * 1024.0 + 0.5), W += 1; iff r < 1.0 also CW += 1 and B, G, R += the
+ * frame's bytes at (ix, iy) (gray three times for one channel).  Synchronous; one
+ * launch reads and writes the volume once whatever nmaps is.  A non-finite P,
+ * origin, voxel or trunc, voxel <= 0, trunc <= 0, a frame index outside the batch,
+ * channels other than 1 or 3, nmaps outside 0..2^20: SLAM_E_INVALID_ARG.  Huge
+ * finite entries are legal and come out invalid.  nmaps == 0: SLAM_OK, no launch. */
+int slam_tsdf_integrate_dev(slam_ctx* ctx, void* stream, int32_t* d_volume, int nx, int ny, int nz, const double* origin,
+                            double voxel, double trunc, const uint8_t* d_frames, int nframes, int w, int h, int channels,
+                            const int32_t* frame_idx, const float* d_inv_depth, const double* P, int nmaps);
+/* Marching cubes on the node lattice.  A node is known iff W >= min_weight (>= 1),
+ * inside iff known and D < 0; cell (i, j, k) is active iff its eight corners are
+ * known.  Corner c = dx | dy << 1 | dz << 2; the edge along `axis` is owned by its
+ * lower corner and has id axis * 4 + the owner's rank among the four corners with
+ * bit axis clear; the triangles of the 256 sign cases are csrc/tsdf_table.h,
+ * generated by the rule in tests/tsdf_ref.py.  Node (i, j, k) owns its +x, +y, +z
+ * edges; an edge carries a vertex iff its far node is in the grid, both ends are
+ * known, exactly one is inside and one of the up to four cells around it is
+ * active.  With a the owner, fa = (double)Da / (double)Wa, fb likewise, t = fa / (fa -
+ * fb): the vertex sits at origin[axis] + ((double)i_axis + t) voxel along the axis
+ * and at the node's coordinates otherwise; per channel a node's colour is ca = CW ?
+ * (2 sum + CW) / (2 CW) : 0 in integers and the vertex's is (uint8)floor(((double)ca
+ * + t ((double)cb - (double)ca)) + 0.5).  Vertices are numbered by owner node in
+ * raster order (z outer, x inner), +x, +y, +z within a node; faces come cell by cell
+ * in raster order, in the table's order within a cell; zero-area triangles are
+ * kept.  Outputs (device): d_vertices cap_vertices x 3 f64, d_colors cap_vertices x
+ * 3 u8 (blue, green, red), d_faces cap_faces x 3 int32.  *nv / *nf = the counts;
+ * when either exceeds its capacity: SLAM_E_CAPACITY with both needed counts and
+ * nothing written.  More than 2^31 - 1 of either: SLAM_E_UNSUPPORTED.  Synchronous. */
+int slam_tsdf_mesh_dev(slam_ctx* ctx, void* stream, const int32_t* d_volume, int nx, int ny, int nz, const double* origin,
+                       double voxel, int min_weight, double* d_vertices, uint8_t* d_colors, int32_t* d_faces,
+                       int cap_vertices, int cap_faces, int* nv, int* nf);
+/* slam_tsdf_integrate_dev for a volume, packed frames (nframes x h x w x channels)
+ * and maps in host memory; the volume is updated in place. */
+int slam_tsdf_integrate(slam_ctx* ctx, int32_t* volume, int nx, int ny, int nz, const double* origin, double voxel,
+                        double trunc, const uint8_t* frames, int nframes, int w, int h, int channels,
+                        const int32_t* frame_idx, const float* inv_depth, const double* P, int nmaps);
+/* slam_tsdf_mesh_dev for a volume and outputs in host memory. */
+int slam_tsdf_mesh(slam_ctx* ctx, const int32_t* volume, int nx, int ny, int nz, const double* origin, double voxel,
+                   int min_weight, double* vertices, uint8_t* colors, int32_t* faces, int cap_vertices, int cap_faces,
+                   int* nv, int* nf);
+/* The host twins: no context, no device, the same arithmetic (csrc/tsdf_math.h, csrc/
+ * tsdf_table.h) on up to 16 threads, the same results and error codes bit for bit. */
+int slam_tsdf_integrate_host(int32_t* volume, int nx, int ny, int nz, const double* origin, double voxel, double trunc,
+                             const uint8_t* frames, int nframes, int w, int h, int channels, const int32_t* frame_idx,
+                             const float* inv_depth, const double* P, int nmaps);
+int slam_tsdf_mesh_host(const int32_t* volume, int nx, int ny, int nz, const double* origin, double voxel, int min_weight,
+                        double* vertices, uint8_t* colors, int32_t* faces, int cap_vertices, int cap_faces, int* nv,
+                        int* nf);
+/* Library HIP-event times (ms) of the context's last slam_tsdf_integrate_dev (ms[0]
+ * tsdf_integrate) and of its last slam_tsdf_mesh_dev (ms[1] tsdf_classify +
+ * tsdf_count, ms[2] tsdf_scan, ms[3] tsdf_emit_vertices + tsdf_emit_faces; 0 when
+ * nothing was emitted); 0 before the first call. */
+int slam_tsdf_last_timing(slam_ctx* ctx, double* ms);
+
 /* ---- place recognition: a flat visual vocabulary and bag-of-words retrieval (place.hip) ----
  * All arithmetic is integer except the one IEEE division of a score, so device,
  * host twin and the numpy contract (tests/place_ref.py) agree bit for bit.

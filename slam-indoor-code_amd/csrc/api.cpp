@@ -429,7 +429,8 @@ void slam_destroy(slam_ctx* c)
                       &c->render_ws, &c->render_in, &c->render_out,
                       &c->mvs_census, &c->mvs_par, &c->mvs_mask, &c->mvs_out, &c->mvs_in,
                       &c->place_part, &c->place_norm, &c->place_word, &c->place_cnt, &c->place_par, &c->place_in,
-                      &c->loop_ws, &c->loop_in, &c->loop_pgo, &c->gba_ws, &c->gba_in};
+                      &c->loop_ws, &c->loop_in, &c->loop_pgo, &c->gba_ws, &c->gba_in,
+                      &c->tsdf_par, &c->tsdf_ws, &c->tsdf_in};
     for (DevBuf* b : bufs) b->release();
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->ev_up) (void)hipEventDestroy(c->ev_up);
@@ -445,6 +446,7 @@ void slam_destroy(slam_ctx* c)
     jpeg_enc_release(c);
     render_release(c);
     mvs_release(c);
+    tsdf_release(c);
     for (auto& f : c->prof)
         for (hipEvent_t e : f.ev) (void)hipEventDestroy(e);
     if (c->ev_sync) (void)hipEventDestroy(c->ev_sync);

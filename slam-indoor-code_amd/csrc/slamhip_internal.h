@@ -379,6 +379,12 @@ struct slam_ctx {
     slamhip::DevBuf loop_pgo;             // slam_pgo_sim3_dev: nodes, linearisations, blocks, PCG vectors, scalars, lists
     // global bundle adjustment (gba.hip): the solver's working set, the staged cameras + points of slam_gba
     slamhip::DevBuf gba_ws, gba_in;
+    // TSDF fusion and marching cubes (tsdf.hip): the per-map parameter block of an integrate call, the
+    // extraction scratch (flags, vertex bases, row counts and bases, totals), the staged buffers of the
+    // host-pointer calls
+    slamhip::DevBuf tsdf_par, tsdf_ws, tsdf_in;
+    hipEvent_t tsdf_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    double tsdf_ms[4] = {0, 0, 0, 0};     // slam_tsdf_last_timing: integrate, classify + count, scan, emit
 
     bool prof_on = false;
     slamhip::ProfFamily prof[slamhip::kProfFamilies];
@@ -703,6 +709,13 @@ void jpeg_enc_release(slam_ctx* c);
 // ---- plane-sweep stereo (mvs.hip) ----
 // destroys the context's timing events
 void mvs_release(slam_ctx* c);
+// ---- TSDF fusion and marching cubes (tsdf.hip, tsdf_host.cpp) ----
+// destroys the context's timing events
+void tsdf_release(slam_ctx* c);
+// argument checks shared by the device entry points and the host twins (tsdf_host.cpp)
+int tsdf_check_volume(const void* volume, int nx, int ny, int nz, const double* origin, double voxel);
+int tsdf_check_maps(double trunc, const void* frames, int nframes, int w, int h, int channels, const int32_t* frame_idx,
+                    const void* inv_depth, const double* P, int nmaps);
 // ---- place recognition (place.hip, place_host.cpp) ----
 // argument checks shared by the device entry points and the host twins (place_host.cpp)
 int place_check_assign(const void* desc, int n, const void* cent, int K, int kind);

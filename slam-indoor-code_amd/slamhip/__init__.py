@@ -33,8 +33,11 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
                   IMWRITE_JPEG_QUALITY, IMWRITE_JPEG_RST_INTERVAL, IMWRITE_JPEG_SAMPLING_FACTOR,
                   IMWRITE_JPEG_SAMPLING_FACTOR_420, IMWRITE_JPEG_SAMPLING_FACTOR_422, IMWRITE_JPEG_SAMPLING_FACTOR_444,
                   renderViews, renderCamera, renderStats,
-                  censusTransform, planeSweepDepth, planeSweepDepthBatch, fuseDepthMaps)
-from .dense import DenseParams, densify, depth_planes, sweep_matrices
+                  censusTransform, planeSweepDepth, planeSweepDepthBatch, fuseDepthMaps,
+                  tsdfIntegrate, tsdfMesh, tsdfLastTiming)
+from .dense import DenseParams, densify, depth_maps, depth_planes, sweep_matrices
+from . import surface
+from .surface import SurfaceParams, projection_matrix, volume_bounds
 from .place import Database, LoopParams, Vocabulary, detect_loops, verify_loop
 from . import place
 from . import loopclose

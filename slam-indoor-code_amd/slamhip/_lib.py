@@ -231,6 +231,13 @@ SIGNATURES = {
     "slam_mvs_fuse": (_I, [_P, _P, _I, _I, _SZ, _I, _I, _P, _P, _P, _P, _P, _P, _P, _D, _I, _I, _I, _P, _P, _I, _P]),
     "slam_mvs_last_timing": (_I, [_P, _P]),
     "slam_mvs_depth_host": (_I, [_P, _P, _I, _I, _I, _SZ, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "slam_tsdf_integrate_dev": (_I, [_P, _P, _P, _I, _I, _I, _P, _D, _D, _P, _I, _I, _I, _I, _P, _P, _P, _I]),
+    "slam_tsdf_mesh_dev": (_I, [_P, _P, _P, _I, _I, _I, _P, _D, _I, _P, _P, _P, _I, _I, _P, _P]),
+    "slam_tsdf_integrate": (_I, [_P, _P, _I, _I, _I, _P, _D, _D, _P, _I, _I, _I, _I, _P, _P, _P, _I]),
+    "slam_tsdf_mesh": (_I, [_P, _P, _I, _I, _I, _P, _D, _I, _P, _P, _P, _I, _I, _P, _P]),
+    "slam_tsdf_integrate_host": (_I, [_P, _I, _I, _I, _P, _D, _D, _P, _I, _I, _I, _I, _P, _P, _P, _I]),
+    "slam_tsdf_mesh_host": (_I, [_P, _I, _I, _I, _P, _D, _I, _P, _P, _P, _I, _I, _P, _P]),
+    "slam_tsdf_last_timing": (_I, [_P, _P]),
     "slam_voc_assign_dev": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P]),
     "slam_voc_train_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "slam_bow_vectors_dev": (_I, [_P, _P, _P, _P, _I, _P, _I, _P, _P]),

@@ -1874,3 +1874,117 @@ def fuseDepthMaps(frames, inv_depth, nbrs, M, v, B, c, eps=0.01, min_consistent=
         e.needed = n_out.value          # SLAM_E_CAPACITY: the count that did not fit
         raise
     return pts[:n_out.value].copy(), cols[:n_out.value].copy()
+
+
+# ---- surface from the depth maps: TSDF fusion and marching cubes ----
+
+def _tsdf_volume(volume, host):
+    """(pointer, nx, ny, nz, resident) of a volume: a resident int32 torch tensor or a host int32 array, (6, nz, ny, nx)"""
+    resident = hasattr(volume, "data_ptr")
+    if resident:
+        import torch
+        if host:
+            raise ValueError("host=True takes a host volume")
+        if volume.dtype != torch.int32 or volume.dim() != 4 or volume.shape[0] != 6 or not volume.is_contiguous():
+            raise ValueError("volume: contiguous int32 (6, nz, ny, nx)")
+        p = ctypes.c_void_p(volume.data_ptr())
+    else:
+        if not isinstance(volume, np.ndarray) or volume.dtype != np.int32 or volume.ndim != 4 or volume.shape[0] != 6 \
+                or not volume.flags.c_contiguous:
+            raise ValueError("volume: contiguous int32 (6, nz, ny, nx)")
+        p = ptr(volume)
+    return p, int(volume.shape[3]), int(volume.shape[2]), int(volume.shape[1]), resident
+
+
+def tsdfIntegrate(volume, frames, inv_depth, P, origin, voxel, trunc, frame_idx=None, ctx=None, host=False):
+    """slam_tsdf_integrate_dev / slam_tsdf_integrate / slam_tsdf_integrate_host: add the depth
+    maps inv_depth (nmaps, h, w) float32 to `volume` (int32 (6, nz, ny, nx), updated in place
+    and returned).  A resident volume takes a resident frame batch (n, h, w[, 3]) and resident
+    maps; a host volume takes host frames (a list or an array) and host maps, on the device or,
+    with host=True, through the host twin: the same bits without a device.  Map m belongs to
+    frame frame_idx[m] (default m) and has the projection P[m] (3 x 4, surface.projection_matrix);
+    origin (3), voxel and trunc describe the grid.  The caller keeps a volume below 2^20 maps
+    in total (surface.fuse_maps counts)."""
+    vp, nx, ny, nz, resident = _tsdf_volume(volume, host)
+    P = np.ascontiguousarray(P, np.float64).reshape(-1, 12)
+    nmaps = len(P)
+    if nmaps > (1 << 20):
+        raise ValueError("at most 2^20 maps per call")
+    fi = None if frame_idx is None else np.ascontiguousarray(frame_idx, np.int32).reshape(nmaps)
+    org = np.ascontiguousarray(origin, np.float64).reshape(3)
+    if resident:
+        import torch
+        h_ctx = _ctx(ctx)
+        fr, n, w, h, ch = _resident(frames)
+        inv = inv_depth if hasattr(inv_depth, "data_ptr") else torch.from_numpy(np.ascontiguousarray(inv_depth, np.float32)).to(fr.device)
+        if inv.dtype != torch.float32 or tuple(inv.shape) != (nmaps, h, w):
+            raise ValueError("inv_depth: float32 (nmaps, h, w)")
+        inv = inv.contiguous()
+        torch.cuda.current_stream(inv.device).synchronize()
+        check(lib().slam_tsdf_integrate_dev(h_ctx, None, vp, nx, ny, nz, ptr(org), float(voxel), float(trunc),
+                                            ctypes.c_void_p(fr.data_ptr()), n, w, h, ch, ptr(fi),
+                                            ctypes.c_void_p(inv.data_ptr()), ptr(P), nmaps), h_ctx)
+        return volume
+    fl, w, h, ch = _mvs_frames(list(frames))
+    fr = np.ascontiguousarray(np.stack(fl))
+    inv = np.ascontiguousarray(inv_depth, np.float32).reshape(nmaps, h, w)
+    tail = (nx, ny, nz, ptr(org), float(voxel), float(trunc), ptr(fr), len(fl), w, h, ch, ptr(fi), ptr(inv), ptr(P), nmaps)
+    if host:
+        check(lib().slam_tsdf_integrate_host(vp, *tail))
+    else:
+        h_ctx = _ctx(ctx)
+        check(lib().slam_tsdf_integrate(h_ctx, vp, *tail), h_ctx)
+    return volume
+
+
+TSDF_MESH_CAP = (1 << 16, 1 << 17)       # tsdfMesh's first try with cap=None: vertices, faces
+
+
+def tsdfMesh(volume, origin, voxel, min_weight=2, cap=None, ctx=None, host=False):
+    """slam_tsdf_mesh_dev / slam_tsdf_mesh / slam_tsdf_mesh_host: marching cubes on the node
+    lattice of `volume` -> (vertices (n, 3) float64, colors (n, 3) uint8 blue-green-red, faces
+    (m, 3) int32).  cap = (vertices, faces) are the output capacities; too small raises
+    SlamError with code SLAM_E_CAPACITY and both needed counts in its `needed`.  With
+    cap=None the call is repeated once with the needed counts."""
+    vp, nx, ny, nz, resident = _tsdf_volume(volume, host)
+    org = np.ascontiguousarray(origin, np.float64).reshape(3)
+    h_ctx = None if host else _ctx(ctx)
+    cv, cf = TSDF_MESH_CAP if cap is None else (int(cap[0]), int(cap[1]))
+    for attempt in (0, 1):
+        nv, nf = ctypes.c_int(0), ctypes.c_int(0)
+        if resident:
+            import torch
+            dev = volume.device
+            torch.cuda.current_stream(dev).synchronize()
+            v = torch.empty((max(cv, 1), 3), dtype=torch.float64, device=dev)
+            c = torch.empty((max(cv, 1), 3), dtype=torch.uint8, device=dev)
+            f = torch.empty((max(cf, 1), 3), dtype=torch.int32, device=dev)
+            rc = lib().slam_tsdf_mesh_dev(h_ctx, None, vp, nx, ny, nz, ptr(org), float(voxel), int(min_weight),
+                                          ctypes.c_void_p(v.data_ptr()), ctypes.c_void_p(c.data_ptr()),
+                                          ctypes.c_void_p(f.data_ptr()), cv, cf, ctypes.byref(nv), ctypes.byref(nf))
+        else:
+            v, c, f = np.empty((max(cv, 1), 3), np.float64), np.empty((max(cv, 1), 3), np.uint8), np.empty((max(cf, 1), 3), np.int32)
+            tail = (nx, ny, nz, ptr(org), float(voxel), int(min_weight), ptr(v), ptr(c), ptr(f), cv, cf, ctypes.byref(nv),
+                    ctypes.byref(nf))
+            rc = lib().slam_tsdf_mesh_host(vp, *tail) if host else lib().slam_tsdf_mesh(h_ctx, vp, *tail)
+        if rc == L.SLAM_E_CAPACITY and cap is None and attempt == 0:
+            cv, cf = nv.value, nf.value
+            continue
+        try:
+            check(rc, h_ctx)
+        except L.SlamError as e:
+            e.needed = (nv.value, nf.value)
+            raise
+        break
+    if resident:
+        return v[:nv.value].cpu().numpy(), c[:nv.value].cpu().numpy(), f[:nf.value].cpu().numpy()
+    return v[:nv.value].copy(), c[:nv.value].copy(), f[:nf.value].copy()
+
+
+def tsdfLastTiming(ctx=None):
+    """slam_tsdf_last_timing: library HIP-event milliseconds of the last integrate call and the
+    last extraction: dict(integrate, classify_count, scan, emit)"""
+    ms = np.zeros(4, np.float64)
+    c = _ctx(ctx)
+    check(lib().slam_tsdf_last_timing(c, ptr(ms)), c)
+    return dict(zip(("integrate", "classify_count", "scan", "emit"), [float(x) for x in ms]))

@@ -1491,7 +1491,7 @@ def define_camera_position(old_deque, last_id, fd):
 
 
 def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK=None, undistort="frames",
-              criteria=(50, 0.01), max_residual=0.01, tracker=None, klt=None, lens_model=None, dense=None, loops=None):
+              criteria=(50, 0.01), max_residual=0.01, tracker=None, klt=None, lens_model=None, dense=None, loops=None, surface=None):
     """src/main.cpp:71-107 slamMain: mainCycle restarts from the last pose until
     the sequence ends, then points.txt / colors.txt.  K (3x3 float64) is
     updated in place by BA, as the reference's calibrationMatrix is.  dist: the
@@ -1535,6 +1535,13 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
     dense_colors.txt in rawOutput's format.  The four result files are unchanged.
     A frame count that differs from the pose count raises.
 
+    surface (opt-in, needs dense; a surface.SurfaceParams): the depth maps of the one
+    sweep are also integrated into a TSDF volume around the sparse cloud and extracted
+    by marching cubes (surface.fuse_maps); the mesh goes to gd.surfaceVertices /
+    gd.surfaceColors / gd.surfaceFaces and, with out_dir, to surface.ply in
+    scene.write_mesh's format.  Every other file is byte-identical with and without it.
+    Without dense it raises ValueError.
+
     loops (opt-in; a place.LoopParams, None keeps, computes and writes nothing): the
     good frames are kept as for dense (both may be set), and after the last cycle
     place.find_loops describes each of them (ops.fast + ops.describe with the run's
@@ -1562,6 +1569,8 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
     Returns (GlobalData, Logs)."""
     if undistort not in ("frames", "points"):
         raise ValueError('undistort: "frames" or "points"')
+    if surface is not None and dense is None:
+        raise ValueError("surface needs dense: the volume is fused from the sweep's depth maps")
     if tracker not in (None, "klt"):
         raise ValueError('tracker: None or "klt"')
     if tracker is not None and dist is not None:
@@ -1618,12 +1627,30 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
             media.close()
     logs.close(gd)
     if dense is not None:
-        from .dense import densify
+        from .dense import depth_maps, fuse_plan, stage_frames
         if len(logs.frames) != len(gd.cameraRotations) or len(logs.frames) != len(gd.spatialCameraPositions) \
                 or any(f is None for f in logs.frames):
             raise RuntimeError(f"dense: {len(logs.frames)} good frames kept for {len(gd.cameraRotations)} final poses")
-        gd.densePoints, gd.denseColors = densify(logs.frames, K, gd.cameraRotations, gd.spatialCameraPositions,
-                                                 gd.spatialPoints, dense, ctx=getattr(ops, "ctx", None))
+        # the sweep runs once: its maps feed the dense points and, with surface, the volume
+        dctx = getattr(ops, "ctx", None)
+        gd.densePoints, gd.denseColors = np.zeros((0, 3), np.float64), np.zeros((0, 3), np.uint8)
+        staged = stage_frames(logs.frames, False) if len(logs.frames) >= 2 else None
+        maps = None
+        if staged is not None:
+            maps = depth_maps(staged, K, gd.cameraRotations, gd.spatialCameraPositions, gd.spatialPoints, dense, ctx=dctx)
+        if maps is not None:
+            gd.densePoints, gd.denseColors = fuse_plan(staged, maps[0], maps[1], dense, ctx=dctx)
+        if surface is not None:
+            from . import surface as surface_mod
+            if maps is None:
+                res = surface_mod._empty()
+            else:
+                res = surface_mod.fuse_maps(staged, maps[0]["ref"], maps[1], K, gd.cameraRotations, gd.spatialCameraPositions,
+                                            gd.spatialPoints, surface, ctx=dctx)
+            gd.surfaceVertices, gd.surfaceColors, gd.surfaceFaces = res
+            if logs.out_dir:
+                from .scene import Mesh, write_mesh
+                write_mesh(res[0], res[1], [Mesh(res[2], res[2])], os.path.join(logs.out_dir, "surface.ply"))
         if logs.out_dir:
             with open(os.path.join(logs.out_dir, "dense_points.txt"), "w") as f:
                 if len(gd.densePoints):

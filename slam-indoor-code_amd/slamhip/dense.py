@@ -166,6 +166,68 @@ def fuse_host(frames, inv, nbrs, M, v, B, c, eps, min_consistent, step, radius):
     return np.concatenate(pts).astype(np.float64), np.concatenate(cols).astype(np.uint8)
 
 
+def stage_frames(frames, host):
+    """the frames as the two paths take them: host arrays (host=True) or one resident
+    torch batch (n, h, w[, 3]); a batch or a list that is staged already passes through"""
+    if host:
+        return [_host_pixels(f) for f in frames]
+    import torch
+    if isinstance(frames, torch.Tensor):
+        return frames
+    if all(getattr(f, "resident", False) for f in frames):
+        from .cycle import device_frames
+        return device_frames(list(frames))[0]
+    return torch.from_numpy(np.stack([_host_pixels(f) for f in frames])).cuda()
+
+
+def depth_maps(frames, K, rotations, positions, sparse_points, params=None, ctx=None, host=False, chunk=8):
+    """The plane-sweep depth map of every reference of a sequence: (plan, inv_depth),
+    with plan as plan() returns it and inv_depth[m] the float32 (h, w) map of frame
+    plan["ref"][m]: a list of host arrays with host=True (slam_mvs_depth_host), else one
+    resident (nref, h, w) tensor.  None when there are fewer than two frames or no
+    reference.  densify and surface.reconstruct both start here."""
+    from . import api
+    params = params or DenseParams()
+    if len(frames) != len(rotations) or len(frames) != len(positions):
+        raise ValueError("depth_maps: one rotation and one position per frame")
+    if len(frames) < 2:
+        return None
+    shape = tuple(frames[0].shape)
+    if any(tuple(f.shape) != shape for f in frames):
+        raise ValueError("depth_maps: frames of one shape")
+    P = plan(shape, K, rotations, positions, sparse_points, params)
+    nr = len(P["ref"])
+    if nr == 0:
+        return None
+    h, w = shape[0], shape[1]
+    st = stage_frames(frames, host)
+    if host:
+        inv = []
+        for m, i in enumerate(P["ref"]):
+            S = len(P["src"][m])
+            inv.append(api.planeSweepDepth(st[i], [st[j] for j in P["src"][m]], P["M"][m, :S], P["v"][m, :S], P["planes"][m],
+                                           params.radius, params.uniq, params.min_views, host=True)[2])
+        return P, inv
+    import torch
+    inv = torch.empty((nr, h, w), dtype=torch.float32, device=st.device)
+    for m0 in range(0, nr, chunk):
+        m1 = min(nr, m0 + chunk)
+        _, _, iv = api.planeSweepDepthBatch(st, P["ref"][m0:m1], P["src"][m0:m1], P["M"][m0:m1], P["v"][m0:m1],
+                                            P["planes"][m0:m1], params.radius, params.uniq, params.min_views, ctx=ctx)
+        inv[m0:m1] = iv
+    return P, inv
+
+
+def fuse_plan(st, P, inv, params, ctx=None, host=False):
+    """the points of depth_maps' result: the pairwise filter and the emission (densify's second half)"""
+    from . import api
+    if host:
+        return fuse_host([st[i] for i in P["ref"]], inv, P["nbr"], P["nbrM"], P["nbrv"], P["B"], P["c"], params.eps,
+                         params.min_consistent, params.step, params.radius)
+    return api.fuseDepthMaps(st, inv, P["nbr"], P["nbrM"], P["nbrv"], P["B"], P["c"], params.eps, params.min_consistent,
+                             params.step, params.radius, frame_idx=P["ref"], ctx=ctx)
+
+
 def densify(frames, K, rotations, positions, sparse_points, params=None, ctx=None, host=False, chunk=8):
     """Dense points of a sequence of good frames: (points (n, 3) float64, colors
     (n, 3) uint8).  frames[i] (ResidentFrames or host arrays of one shape) has the
@@ -175,7 +237,6 @@ def densify(frames, K, rotations, positions, sparse_points, params=None, ctx=Non
     neighbours that are references themselves and emitted reference after reference.
     host=True computes the depth maps with slam_mvs_depth_host and fuses in numpy:
     the same points bit for bit, without a device."""
-    from . import api
     params = params or DenseParams()
     if len(frames) != len(rotations) or len(frames) != len(positions):
         raise ValueError("densify: one rotation and one position per frame")
@@ -185,31 +246,8 @@ def densify(frames, K, rotations, positions, sparse_points, params=None, ctx=Non
     shape = frames[0].shape
     if any(f.shape != shape for f in frames):
         raise ValueError("densify: frames of one shape")
-    P = plan(shape, K, rotations, positions, sparse_points, params)
-    nr = len(P["ref"])
-    if nr == 0:
+    st = stage_frames(frames, host)
+    got = depth_maps(st, K, rotations, positions, sparse_points, params, ctx=ctx, host=host, chunk=chunk)
+    if got is None:
         return empty
-    h, w = shape[0], shape[1]
-    if host:
-        px = [_host_pixels(f) for f in frames]
-        inv = []
-        for m, i in enumerate(P["ref"]):
-            S = len(P["src"][m])
-            inv.append(api.planeSweepDepth(px[i], [px[j] for j in P["src"][m]], P["M"][m, :S], P["v"][m, :S], P["planes"][m],
-                                           params.radius, params.uniq, params.min_views, host=True)[2])
-        return fuse_host([px[i] for i in P["ref"]], inv, P["nbr"], P["nbrM"], P["nbrv"], P["B"], P["c"], params.eps,
-                         params.min_consistent, params.step, params.radius)
-    import torch
-    if all(getattr(f, "resident", False) for f in frames):
-        from .cycle import device_frames
-        dev, _ = device_frames(list(frames))
-    else:
-        dev = torch.from_numpy(np.stack([_host_pixels(f) for f in frames])).cuda()
-    inv = torch.empty((nr, h, w), dtype=torch.float32, device=dev.device)
-    for m0 in range(0, nr, chunk):
-        m1 = min(nr, m0 + chunk)
-        _, _, iv = api.planeSweepDepthBatch(dev, P["ref"][m0:m1], P["src"][m0:m1], P["M"][m0:m1], P["v"][m0:m1],
-                                            P["planes"][m0:m1], params.radius, params.uniq, params.min_views, ctx=ctx)
-        inv[m0:m1] = iv
-    return api.fuseDepthMaps(dev, inv, P["nbr"], P["nbrM"], P["nbrv"], P["B"], P["c"], params.eps, params.min_consistent,
-                             params.step, params.radius, frame_idx=P["ref"], ctx=ctx)
+    return fuse_plan(st, got[0], got[1], params, ctx=ctx, host=host)

@@ -172,6 +172,37 @@ def write_mesh(global_points, colors, meshes, path):
             f.write(f"3 {int(t[0])} {int(t[1])} {int(t[2])}\n")
 
 
+def load_surface(path):
+    """write_mesh's own ASCII PLY back: (vertices (n, 3) float64 holding the float32 values of the file,
+    colors (n, 3) uint8 blue-green-red, faces (m, 3) int32).  slam_main(surface=...) writes surface.ply
+    in this form.  Anything but write_mesh's header raises ValueError."""
+    with open(path) as f:
+        lines = f.read().split("\n")
+    try:
+        end = lines.index("end_header")
+    except ValueError:
+        raise ValueError(f"{path}: no PLY header")
+    head = lines[:end]
+    if head[:2] != ["ply", "format ascii 1.0"]:
+        raise ValueError(f"{path}: not an ASCII PLY")
+    counts = {h.split()[1]: int(h.split()[2]) for h in head if h.startswith("element ")}
+    props = [h for h in head if h.startswith("property ")]
+    if sorted(counts) != ["face", "vertex"] or props != [
+            "property float x", "property float y", "property float z", "property uchar red", "property uchar green",
+            "property uchar blue", "property list uchar int vertex_indices"]:
+        raise ValueError(f"{path}: not a mesh written by write_mesh")
+    nv, nf = counts["vertex"], counts["face"]
+    body = lines[end + 1:]
+    if len(body) < nv + nf:
+        raise ValueError(f"{path}: truncated")
+    vt = np.array([r.split() for r in body[:nv]], np.float64).reshape(nv, 6)
+    fc = np.array([r.split() for r in body[nv:nv + nf]], np.int64).reshape(nf, 4)
+    if nf and not (fc[:, 0] == 3).all():
+        raise ValueError(f"{path}: a face that is not a triangle")
+    return (np.ascontiguousarray(vt[:, :3]), np.ascontiguousarray(vt[:, 5:2:-1]).astype(np.uint8),
+            np.ascontiguousarray(fc[:, 1:]).astype(np.int32))
+
+
 GREEN, RED, BLUE = (0, 255, 0), (0, 0, 255), (255, 0, 0)     # viz::Color, blue-green-red
 # Point3f centroid(-0.368855, 0.538447, 7.92543), vizualizeCameras:56: narrowed to float, then an Affine3d
 REFERENCE_VIEWER_POSITION = np.array([-0.368855, 0.538447, 7.92543], np.float32).astype(np.float64)
@@ -355,17 +386,29 @@ def main(config_path, render=None, cloud="sparse"):
     were rendered and writes one Motion-JPEG AVI.  The default writes nothing more.
     cloud="dense" works on the dense cloud of slam_main(dense=...) instead, cloud="closed"
     on the corrected cameras and merged cloud of slam_main(loops=LoopParams(close=True)),
-    cloud="refined" on that map after global bundle adjustment (global_ba=True)."""
+    cloud="refined" on that map after global bundle adjustment (global_ba=True).
+    cloud="surface" draws the surface of slam_main(surface=...): the cameras come from the
+    sparse files, surface.ply's vertices are the cloud and its faces one Mesh; nothing is
+    segmented and neither clusters.txt nor mesh.ply is written (returns no segments)."""
     cfg = ConfigService()
     cfg.setConfigFile(config_path)
     if not cfg.getValue("onlyViz"):
         raise ValueError("scene.main handles onlyViz = true; run cycle.slam_main first, then scene.segment")
     out_dir = cfg.getValue("outputDataDir")
-    gd = load_global_data(out_dir, cloud)
-    segments = segment(gd, cfg)
-    write_clusters(segments, os.path.join(out_dir, "clusters.txt"))
-    meshes = mesh(segments)
-    write_mesh(gd.spatialPoints, gd.spatialPointsColors, meshes, os.path.join(out_dir, "mesh.ply"))
+    if cloud == "surface":
+        gd = load_global_data(out_dir)
+        verts, cols, faces = load_surface(os.path.join(out_dir, "surface.ply"))
+        cams = gd
+        gd = GlobalData()
+        gd.spatialCameraPositions, gd.cameraRotations = cams.spatialCameraPositions, cams.cameraRotations
+        gd.push_points(verts, cols)
+        segments, meshes = [], [Mesh(faces, faces)]
+    else:
+        gd = load_global_data(out_dir, cloud)
+        segments = segment(gd, cfg)
+        write_clusters(segments, os.path.join(out_dir, "clusters.txt"))
+        meshes = mesh(segments)
+        write_mesh(gd.spatialPoints, gd.spatialPointsColors, meshes, os.path.join(out_dir, "mesh.ply"))
     if render is not None:
         draw = render_scene
         if isinstance(render, str):
