@@ -1192,6 +1192,79 @@ int slam_mvs_depth_host(const uint8_t* ref, const uint8_t* const* srcs, int S, i
                         const double* M, const double* v, const double* planes, int D, int radius, int uniq,
                         int min_views, int16_t* plane, int32_t* cost, float* inv_depth);
 
+/* ---- semi-global aggregation of the plane-sweep cost volume (mvs_sgm.hip) ---------- */
+/* An opt-in rule beside the winner-take-all of slam_mvs_depth_batch_dev (DESIGN.md
+ * section 28).  The definition of every value is tests/mvs_sgm_ref.py; the device
+ * and the host twins equal it bit for bit (integers only, so no schedule matters).
+ * The reference has no such stage.
+ *
+ * Volume: C[d] and nvalid[d] exactly as slam_mvs_depth_batch_dev defines them, C <=
+ * 64 (2 radius + 1)^2 S <= 12544 as uint16, nvalid as uint8, both h x w x D per
+ * reference with the plane index innermost.
+ * Paths: steps (dx, dy) in the order (1,0) (-1,0) (0,1) (0,-1) (1,1) (-1,-1) (1,-1)
+ * (-1,1); paths = 4 takes the first four, 8 all.  For path r and q = p - r:
+ * L_r(p, d) = C(p, d) when q is outside the image, else with m = min_k L_r(q, k)
+ *   L_r(p, d) = C(p, d) + min(L_r(q, d), L_r(q, d - 1) + P1, L_r(q, d + 1) + P1, m + P2) - m,
+ * the d - 1 and d + 1 terms absent at the two end planes.  C <= L_r <= C + P2 fits
+ * uint16; S(p, d) = the sum of L_r over the paths <= 8 * 65535 fits int32.
+ * Penalties: the caller's p1, p2 (0 <= p1 <= p2 <= 255) are per window pixel and
+ * source in Hamming bits; a reference with S sources at radius r uses P1 = p1 (2 r +
+ * 1)^2 S and P2 likewise, so one setting means the same at every radius and S.
+ * Winner: the rule of slam_mvs_depth_batch_dev on S in place of C (best, second,
+ * uniq, nvalid[best] >= min_views, the parabola): plane = best, cost = S[best],
+ * inv_depth.  With p1 = p2 = 0 every L_r is C: plane and inv_depth equal the
+ * winner-take-all result bit for bit and cost is paths times its cost.
+ *
+ * slam_mvs_cost_volume_dev: the volume alone of nref references (arguments as
+ * slam_mvs_depth_batch_dev) into d_C and d_nvalid (device, nref x h x w x D).
+ * Synchronous; the errors of slam_mvs_depth_batch_dev. */
+int slam_mvs_cost_volume_dev(slam_ctx* ctx, void* stream, const uint8_t* d_frames, int nframes, int w, int h, int channels,
+                             int nref, const int32_t* ref_idx, const int32_t* nsrc, const int32_t* src_idx, const double* M,
+                             const double* v, const double* planes, int D, int radius, uint16_t* d_C, uint8_t* d_nvalid);
+/* S of n given volumes (d_C: n x h x w x D uint16, device, every value <= 12544)
+ * with the effective penalties P1 <= P2 <= 65535 - 12544 into d_S (n x h x w x D
+ * int32, device).  n 0..65535, D 4..256, paths 4 or 8, else SLAM_E_INVALID_ARG; w >
+ * 4096: SLAM_E_UNSUPPORTED.  Synchronous. */
+int slam_mvs_sgm_aggregate_dev(slam_ctx* ctx, void* stream, const uint16_t* d_C, int n, int w, int h, int D, int P1, int P2,
+                               int paths, int32_t* d_S);
+/* slam_mvs_depth_batch_dev with the aggregation between the volume and the winner.
+ * The references are worked through in groups whose scratch (7 bytes per pixel and
+ * plane: C, nvalid, S) stays under the context's budget (8 GiB unless
+ * slam_mvs_sgm_set_budget says otherwise; a single reference that exceeds it still
+ * runs alone); the results do not depend on the grouping.  p1 > p2, either outside
+ * 0..255 or paths not 4 or 8: SLAM_E_INVALID_ARG, as is everything
+ * slam_mvs_depth_batch_dev refuses; w > 4096: SLAM_E_UNSUPPORTED. */
+int slam_mvs_depth_sgm_batch_dev(slam_ctx* ctx, void* stream, const uint8_t* d_frames, int nframes, int w, int h,
+                                 int channels, int nref, const int32_t* ref_idx, const int32_t* nsrc,
+                                 const int32_t* src_idx, const double* M, const double* v, const double* planes, int D,
+                                 int radius, int uniq, int min_views, int p1, int p2, int paths, int16_t* d_plane,
+                                 int32_t* d_cost, float* d_inv_depth);
+/* slam_mvs_depth_sgm_batch_dev for one reference and its S sources in host memory,
+ * as slam_mvs_depth is to slam_mvs_depth_batch_dev. */
+int slam_mvs_depth_sgm(slam_ctx* ctx, const uint8_t* ref, const uint8_t* const* srcs, int S, int w, int h, size_t step,
+                       int channels, const double* M, const double* v, const double* planes, int D, int radius, int uniq,
+                       int min_views, int p1, int p2, int paths, int16_t* plane, int32_t* cost, float* inv_depth);
+/* the scratch budget in bytes of the context's later slam_mvs_depth_sgm_batch_dev
+ * calls; 0 = the default (8 GiB).  Never changes results. */
+int slam_mvs_sgm_set_budget(slam_ctx* ctx, size_t bytes);
+/* HIP-event times (ms) of the context's last slam_mvs_depth_sgm_batch_dev, summed
+ * over its groups: ms[0] mvs_volume, ms[1] the clear of S + sgm_path, ms[2]
+ * sgm_winner.  slam_mvs_cost_volume_dev sets ms[0], slam_mvs_sgm_aggregate_dev
+ * ms[1] alone.  0 before the first call. */
+int slam_mvs_sgm_last_timing(slam_ctx* ctx, double* ms);
+/* The host twins: no context, no device, the same arithmetic (csrc/mvs_sgm_math.h)
+ * on up to 16 threads, the same results bit for bit.  slam_mvs_cost_volume_host:
+ * the volume of one reference (C, nvalid: h x w x D).  slam_mvs_sgm_aggregate_host:
+ * slam_mvs_sgm_aggregate_dev on host memory.  slam_mvs_depth_sgm_host:
+ * slam_mvs_depth_sgm. */
+int slam_mvs_cost_volume_host(const uint8_t* ref, const uint8_t* const* srcs, int S, int w, int h, size_t step, int channels,
+                              const double* M, const double* v, const double* planes, int D, int radius, uint16_t* C,
+                              uint8_t* nvalid);
+int slam_mvs_sgm_aggregate_host(const uint16_t* C, int n, int w, int h, int D, int P1, int P2, int paths, int32_t* S);
+int slam_mvs_depth_sgm_host(const uint8_t* ref, const uint8_t* const* srcs, int S, int w, int h, size_t step, int channels,
+                            const double* M, const double* v, const double* planes, int D, int radius, int uniq,
+                            int min_views, int p1, int p2, int paths, int16_t* plane, int32_t* cost, float* inv_depth);
+
 /* ---- surface from the depth maps: TSDF fusion and marching cubes (tsdf.hip) -------- */
 /* An opt-in stage after the depth maps.  The definition of
  * every value is tests/tsdf_ref.py; the device and the host twins equal it bit for

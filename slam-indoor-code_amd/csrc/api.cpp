@@ -427,7 +427,7 @@ void slam_destroy(slam_ctx* c)
                       &c->jpeg_in, &c->jpeg_coef, &c->jpeg_planes, &c->jpeg_out, &c->jpeg_sync,
                       &c->jenc_ws, &c->jenc_coef, &c->jenc_bits, &c->jenc_ff, &c->jenc_io,
                       &c->render_ws, &c->render_in, &c->render_out,
-                      &c->mvs_census, &c->mvs_par, &c->mvs_mask, &c->mvs_out, &c->mvs_in,
+                      &c->mvs_census, &c->mvs_par, &c->mvs_mask, &c->mvs_out, &c->mvs_in, &c->mvs_sgm,
                       &c->place_part, &c->place_norm, &c->place_word, &c->place_cnt, &c->place_par, &c->place_in,
                       &c->loop_ws, &c->loop_in, &c->loop_pgo, &c->gba_ws, &c->gba_in,
                       &c->tsdf_par, &c->tsdf_ws, &c->tsdf_in};

@@ -11,6 +11,9 @@
 //               separable (rows, then columns); the winner rule streams in
 //               registers (MvsPixel), so the cost volume never exists.  The part of
 //               the projection no plane changes (q) is computed once per position.
+//   mvs_volume  the same plane loop (mvs_plane_loop) with another sink: C and nvalid
+//               of every plane are stored, the plane index innermost, for the
+//               semi-global aggregation of mvs_sgm.hip.
 //   mvs_filter  the pairwise consistency test, one thread per pixel, one 64-bit
 //               ballot per row segment.
 //   mvs_count / mvs_emit
@@ -96,13 +99,17 @@ struct SweepParams {
     const int32_t* list;         // the references this launch sweeps (all of one S)
     const double* planes;        // nref x D
     int w, h, D, radius, uniq, min_views;
-    int16_t* plane;              // nref x h x w each
+    int16_t* plane;              // nref x h x w each (mvs_sweep)
     int32_t* cost;
     float* inv;
+    uint16_t* vol_C;             // nref x h x w x D each (mvs_volume)
+    uint8_t* vol_nv;
 };
 
-template <int S>
-__global__ __launch_bounds__(kThreads) void mvs_sweep(SweepParams p)
+// The plane loop shared by mvs_sweep and mvs_volume: the sink is told its two pixels (begin), then
+// every plane's box-summed cost and valid count of each in plane order (plane), then the end (finish).
+template <int S, class Sink>
+__device__ __forceinline__ void mvs_plane_loop(const SweepParams& p, Sink& sink)
 {
     __shared__ int32_t raw[2][kSwLH][kSwPitch];     // cost | nvalid << 16 of the tile + halo, two planes
     __shared__ int32_t hs[kSwLH][kSwTW + 1];        // row sums
@@ -147,10 +154,12 @@ __global__ __launch_bounds__(kThreads) void mvs_sweep(SweepParams p)
             for (int s = 0; s < S; s++) mvs_q(R.M[s], X, Y, q[k][s]);
         }
     }
-    MvsPixel st[2];
-    mvs_pixel_init(st[0]);
-    mvs_pixel_init(st[1]);
     const int tx = tid & (kSwTW - 1), ty = tid / kSwTW;     // pixel rows ty and ty + 8
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int X = X0 + tx, Y = Y0 + ty + 8 * j;
+        sink.begin(j, X < w && Y < h, (size_t)ri * npx + (size_t)Y * w + X);
+    }
     __syncthreads();
 
     for (int d = 0; d < D; d++) {
@@ -187,19 +196,86 @@ __global__ __launch_bounds__(kThreads) void mvs_sweep(SweepParams p)
             const int y = ty + 8 * j;
             int32_t C = 0;
             for (int dy = 0; dy <= 2 * r; dy++) C += hs[y + dy][tx];
-            mvs_pixel_update(st[j], d, C, rw[(y + r) * kSwPitch + tx + r] >> 16);
+            sink.plane(j, d, C, rw[(y + r) * kSwPitch + tx + r] >> 16, p);
         }
         // the next plane writes the other half of raw; its first barrier orders hs
     }
 
 #pragma unroll
-    for (int j = 0; j < 2; j++) {
-        const int X = X0 + tx, Y = Y0 + ty + 8 * j;
-        if (X < w && Y < h) {
-            const size_t o = (size_t)ri * npx + (size_t)Y * w + X;
-            mvs_pixel_finish(st[j], wpl, D, p.uniq, p.min_views, &p.plane[o], &p.cost[o], &p.inv[o]);
+    for (int j = 0; j < 2; j++) sink.finish(j, p, wpl);
+}
+
+// the winner rule streamed in registers: the cost volume never exists
+struct WinnerSink {
+    MvsPixel st[2];
+    size_t o[2];
+    bool in[2];
+    __device__ __forceinline__ void begin(int j, bool inside, size_t pixel)
+    {
+        mvs_pixel_init(st[j]);
+        in[j] = inside;
+        o[j] = pixel;
+    }
+    __device__ __forceinline__ void plane(int j, int d, int32_t C, int32_t nv, const SweepParams&)
+    {
+        mvs_pixel_update(st[j], d, C, nv);
+    }
+    __device__ __forceinline__ void finish(int j, const SweepParams& p, const double* wpl)
+    {
+        if (in[j]) mvs_pixel_finish(st[j], wpl, p.D, p.uniq, p.min_views, &p.plane[o[j]], &p.cost[o[j]], &p.inv[o[j]]);
+    }
+};
+
+template <int S>
+__global__ __launch_bounds__(kThreads) void mvs_sweep(SweepParams p)
+{
+    WinnerSink sink;
+    mvs_plane_loop<S>(p, sink);
+}
+
+// The volume itself, the plane index innermost.  With D a multiple of 8 (Vec) a pixel's costs are staged
+// eight planes at a time in a 128-bit shift register and leave as one 16-byte store (the valid counts as
+// one 8-byte store); any other D stores plane by plane.
+template <bool Vec>
+struct VolumeSink {
+    uint32_t cw[2][4], nw[2][2];
+    size_t o[2];
+    bool in[2];
+    __device__ __forceinline__ void begin(int j, bool inside, size_t pixel)
+    {
+        in[j] = inside;
+        o[j] = pixel;
+        cw[j][0] = cw[j][1] = cw[j][2] = cw[j][3] = nw[j][0] = nw[j][1] = 0;
+    }
+    __device__ __forceinline__ void plane(int j, int d, int32_t C, int32_t nv, const SweepParams& p)
+    {
+        if (!in[j]) return;
+        if (Vec) {
+            cw[j][0] = (cw[j][0] >> 16) | (cw[j][1] << 16);
+            cw[j][1] = (cw[j][1] >> 16) | (cw[j][2] << 16);
+            cw[j][2] = (cw[j][2] >> 16) | (cw[j][3] << 16);
+            cw[j][3] = (cw[j][3] >> 16) | ((uint32_t)C << 16);
+            nw[j][0] = (nw[j][0] >> 8) | (nw[j][1] << 24);
+            nw[j][1] = (nw[j][1] >> 8) | ((uint32_t)nv << 24);
+            if ((d & 7) == 7) {
+                const size_t e = o[j] * p.D + (d - 7);       // a multiple of 8 elements: 16- and 8-byte aligned
+                *reinterpret_cast<uint4*>(p.vol_C + e) = make_uint4(cw[j][0], cw[j][1], cw[j][2], cw[j][3]);
+                *reinterpret_cast<uint2*>(p.vol_nv + e) = make_uint2(nw[j][0], nw[j][1]);
+            }
+        } else {
+            const size_t e = o[j] * p.D + d;
+            p.vol_C[e] = (uint16_t)C;
+            p.vol_nv[e] = (uint8_t)nv;
         }
     }
+    __device__ __forceinline__ void finish(int, const SweepParams&, const double*) {}
+};
+
+template <int S, bool Vec>
+__global__ __launch_bounds__(kThreads) void mvs_volume(SweepParams p)
+{
+    VolumeSink<Vec> sink;
+    mvs_plane_loop<S>(p, sink);
 }
 
 // ---- filter and emit ---------------------------------------------------------------
@@ -346,6 +422,10 @@ void mvs_release(slam_ctx* c)
         if (e) (void)hipEventDestroy(e);
         e = nullptr;
     }
+    for (auto& e : c->sgm_ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
 }
 
 }  // namespace slamhip
@@ -372,17 +452,23 @@ extern "C" int slam_mvs_census_dev(slam_ctx* c, void* stream, const uint8_t* d_f
     return stream_sync(c, s);
 }
 
-extern "C" int slam_mvs_depth_batch_dev(slam_ctx* c, void* stream, const uint8_t* d_frames, int nframes, int w, int h,
-                                        int channels, int nref, const int32_t* ref_idx, const int32_t* nsrc,
-                                        const int32_t* src_idx, const double* M, const double* v, const double* planes,
-                                        int D, int radius, int uniq, int min_views, int16_t* d_plane, int32_t* d_cost,
-                                        float* d_inv_depth)
+// slam_mvs_depth_batch_dev (out.C null: mvs_sweep into plane, cost, inv) and the volume of the same
+// references (out.C set: mvs_volume into C, nvalid); check_only stops after the argument checks.
+// ms[0] census, ms[1] the sweep or volume launches.
+int slamhip::mvs_batch_run(slam_ctx* c, void* stream, const uint8_t* d_frames, int nframes, int w, int h, int channels,
+                           int nref, const int32_t* ref_idx, const int32_t* nsrc, const int32_t* src_idx, const double* M,
+                           const double* v, const double* planes, int D, int radius, int uniq, int min_views,
+                           const MvsBatchOut& out, bool check_only, double* ms)
 {
-    if (!c) return SLAM_E_INVALID_ARG;
+    int16_t* d_plane = out.plane;
+    int32_t* d_cost = out.cost;
+    float* d_inv_depth = out.inv;
+    const bool volume = out.C != nullptr;
     if (!frame_args_ok(nframes, w, h, channels) || !d_frames || nref < 0 || nref > 65535)
         return set_err(c, SLAM_E_INVALID_ARG, "mvs depth: bad frame arguments");
     if (nref == 0) return SLAM_OK;
-    if (!ref_idx || !nsrc || !src_idx || !M || !v || !planes || !d_plane || !d_cost || !d_inv_depth)
+    if (!ref_idx || !nsrc || !src_idx || !M || !v || !planes ||
+        (volume ? !out.nvalid : (!d_plane || !d_cost || !d_inv_depth)))
         return set_err(c, SLAM_E_INVALID_ARG, "mvs depth: null argument");
     std::vector<MvsRefDesc> refs((size_t)nref);
     std::vector<int32_t> slot_of((size_t)nframes, -1), frames_used;
@@ -415,6 +501,7 @@ extern "C" int slam_mvs_depth_batch_dev(slam_ctx* c, void* stream, const uint8_t
             memcpy(R.v[s], v + (size_t)i * 12 + 3 * s, 3 * sizeof(double));
         }
     }
+    if (check_only) return SLAM_OK;
     SLAM_HIP(c, hipSetDevice(c->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
     const size_t npx = (size_t)w * h;
@@ -461,25 +548,57 @@ extern "C" int slam_mvs_depth_batch_dev(slam_ctx* c, void* stream, const uint8_t
     p.plane = d_plane;
     p.cost = d_cost;
     p.inv = d_inv_depth;
+    p.vol_C = out.C;
+    p.vol_nv = out.nvalid;
+    // the staged stores need whole, aligned groups of eight planes
+    const bool vec = D % 8 == 0 && reinterpret_cast<uintptr_t>(out.C) % 16 == 0 && reinterpret_cast<uintptr_t>(out.nvalid) % 8 == 0;
     const int gx = (w + kSwTW - 1) / kSwTW, gy = (h + kSwTH - 1) / kSwTH;
     for (int S = 1; S <= kMvsMaxSources; S++) {
         const int n = first[S + 1] - first[S];
         if (n == 0) continue;
         p.list = reinterpret_cast<const int32_t*>(dpar + o_list) + first[S];
         const dim3 grid(gx, gy, n);
-        switch (S) {
-        case 1: hipLaunchKernelGGL(mvs_sweep<1>, grid, dim3(kThreads), 0, s, p); break;
-        case 2: hipLaunchKernelGGL(mvs_sweep<2>, grid, dim3(kThreads), 0, s, p); break;
-        case 3: hipLaunchKernelGGL(mvs_sweep<3>, grid, dim3(kThreads), 0, s, p); break;
-        default: hipLaunchKernelGGL(mvs_sweep<4>, grid, dim3(kThreads), 0, s, p); break;
+        if (volume) {
+            switch (S * 2 + (vec ? 1 : 0)) {
+            case 2: hipLaunchKernelGGL((mvs_volume<1, false>), grid, dim3(kThreads), 0, s, p); break;
+            case 3: hipLaunchKernelGGL((mvs_volume<1, true>), grid, dim3(kThreads), 0, s, p); break;
+            case 4: hipLaunchKernelGGL((mvs_volume<2, false>), grid, dim3(kThreads), 0, s, p); break;
+            case 5: hipLaunchKernelGGL((mvs_volume<2, true>), grid, dim3(kThreads), 0, s, p); break;
+            case 6: hipLaunchKernelGGL((mvs_volume<3, false>), grid, dim3(kThreads), 0, s, p); break;
+            case 7: hipLaunchKernelGGL((mvs_volume<3, true>), grid, dim3(kThreads), 0, s, p); break;
+            case 8: hipLaunchKernelGGL((mvs_volume<4, false>), grid, dim3(kThreads), 0, s, p); break;
+            default: hipLaunchKernelGGL((mvs_volume<4, true>), grid, dim3(kThreads), 0, s, p); break;
+            }
+        } else {
+            switch (S) {
+            case 1: hipLaunchKernelGGL(mvs_sweep<1>, grid, dim3(kThreads), 0, s, p); break;
+            case 2: hipLaunchKernelGGL(mvs_sweep<2>, grid, dim3(kThreads), 0, s, p); break;
+            case 3: hipLaunchKernelGGL(mvs_sweep<3>, grid, dim3(kThreads), 0, s, p); break;
+            default: hipLaunchKernelGGL(mvs_sweep<4>, grid, dim3(kThreads), 0, s, p); break;
+            }
         }
         SLAM_HIP(c, hipGetLastError());
     }
     SLAM_HIP(c, hipEventRecord(c->mvs_ev[2], s));
     if (int rc = stream_sync(c, s)) return rc;      // the parameter block is reused by the next call
-    c->mvs_ms[0] = mvs_elapsed(c->mvs_ev[0], c->mvs_ev[1]);
-    c->mvs_ms[1] = mvs_elapsed(c->mvs_ev[1], c->mvs_ev[2]);
+    ms[0] = mvs_elapsed(c->mvs_ev[0], c->mvs_ev[1]);
+    ms[1] = mvs_elapsed(c->mvs_ev[1], c->mvs_ev[2]);
     return SLAM_OK;
+}
+
+extern "C" int slam_mvs_depth_batch_dev(slam_ctx* c, void* stream, const uint8_t* d_frames, int nframes, int w, int h,
+                                        int channels, int nref, const int32_t* ref_idx, const int32_t* nsrc,
+                                        const int32_t* src_idx, const double* M, const double* v, const double* planes,
+                                        int D, int radius, int uniq, int min_views, int16_t* d_plane, int32_t* d_cost,
+                                        float* d_inv_depth)
+{
+    if (!c) return SLAM_E_INVALID_ARG;
+    MvsBatchOut out;
+    out.plane = d_plane;
+    out.cost = d_cost;
+    out.inv = d_inv_depth;
+    return mvs_batch_run(c, stream, d_frames, nframes, w, h, channels, nref, ref_idx, nsrc, src_idx, M, v, planes, D, radius,
+                         uniq, min_views, out, false, c->mvs_ms);
 }
 
 extern "C" int slam_mvs_fuse_dev(slam_ctx* c, void* stream, const uint8_t* d_frames, int nframes, int w, int h,

@@ -50,25 +50,14 @@ int mvs_check_args(int S, int w, int h, int channels, const double* M, const dou
     return SLAM_OK;
 }
 
-}  // namespace slamhip
-
-using namespace slamhip;
-
-extern "C" int slam_mvs_depth_host(const uint8_t* ref, const uint8_t* const* srcs, int S, int w, int h, size_t step,
-                                   int channels, const double* M, const double* v, const double* planes, int D,
-                                   int radius, int uniq, int min_views, int16_t* plane, int32_t* cost, float* inv_depth)
+// The plane loop of one reference over census maps cen ((S + 1) x h x w, the reference first): rows are
+// dealt to up to 16 threads, a thread sweeps the planes over its band and hands sink(x, y, d, C, nvalid)
+// every pixel of every plane, planes in order.  Shared by slam_mvs_depth_host and mvs_cost_volume_host.
+template <class Sink>
+static void sweep_bands(const uint64_t* cen, int S, int w, int h, const double* M, const double* v, const double* planes,
+                        int D, int radius, Sink sink)
 {
-    if (!ref || !srcs || !plane || !cost || !inv_depth) return SLAM_E_INVALID_ARG;
-    if (int rc = mvs_check_args(S, w, h, channels, M, v, planes, D, radius, uniq, min_views)) return rc;
-    if (step < (size_t)w * channels) return SLAM_E_INVALID_ARG;
-    for (int s = 0; s < S; s++)
-        if (!srcs[s]) return SLAM_E_INVALID_ARG;
-
     const size_t npx = (size_t)w * h;
-    std::vector<uint64_t> cen((size_t)(S + 1) * npx);
-    mvs_census_host(ref, w, h, step, channels, cen.data());
-    for (int s = 0; s < S; s++) mvs_census_host(srcs[s], w, h, step, channels, cen.data() + (size_t)(s + 1) * npx);
-
     const int r = radius;
     // bands of at least 16 rows: a band repeats the `radius` rows above and below it
     const int nthreads = std::max(1, std::min({16, (int)std::thread::hardware_concurrency(), (h + 15) / 16}));
@@ -84,8 +73,6 @@ extern "C" int slam_mvs_depth_host(const uint8_t* ref, const uint8_t* const* src
                 for (int s = 0; s < S; s++) mvs_q(M + 9 * s, x, y, &q[(((size_t)(y - lo) * w + x) * S + s) * 3]);
         std::vector<int32_t> raw((size_t)nr * w), hs((size_t)nr * w);
         std::vector<uint8_t> nval((size_t)nr * w);
-        std::vector<MvsPixel> st((size_t)(y1 - y0) * w);
-        for (auto& p : st) mvs_pixel_init(p);
         for (int d = 0; d < D; d++) {
             for (int y = lo; y <= hi; y++)
                 for (int x = 0; x < w; x++) {
@@ -115,14 +102,9 @@ extern "C" int slam_mvs_depth_host(const uint8_t* ref, const uint8_t* const* src
                 for (int x = 0; x < w; x++) {
                     int32_t C = 0;
                     for (int dy = -r; dy <= r; dy++) C += hs[(size_t)(mvs_clamp(y + dy, 0, h - 1) - lo) * w + x];
-                    mvs_pixel_update(st[(size_t)(y - y0) * w + x], d, C, nval[(size_t)(y - lo) * w + x]);
+                    sink(x, y, d, C, (int32_t)nval[(size_t)(y - lo) * w + x]);
                 }
         }
-        for (int y = y0; y < y1; y++)
-            for (int x = 0; x < w; x++) {
-                const size_t i = (size_t)y * w + x;
-                mvs_pixel_finish(st[(size_t)(y - y0) * w + x], planes, D, uniq, min_views, &plane[i], &cost[i], &inv_depth[i]);
-            }
     };
     if (nthreads == 1) {
         band(0);
@@ -132,5 +114,52 @@ extern "C" int slam_mvs_depth_host(const uint8_t* ref, const uint8_t* const* src
         band(0);
         for (auto& th : pool) th.join();
     }
+}
+
+static std::vector<uint64_t> census_all(const uint8_t* ref, const uint8_t* const* srcs, int S, int w, int h, size_t step,
+                                        int channels)
+{
+    const size_t npx = (size_t)w * h;
+    std::vector<uint64_t> cen((size_t)(S + 1) * npx);
+    mvs_census_host(ref, w, h, step, channels, cen.data());
+    for (int s = 0; s < S; s++) mvs_census_host(srcs[s], w, h, step, channels, cen.data() + (size_t)(s + 1) * npx);
+    return cen;
+}
+
+// C and nvalid of one reference in the public layout (h x w x D, the plane innermost); arguments checked by the caller
+void mvs_cost_volume_host(const uint8_t* ref, const uint8_t* const* srcs, int S, int w, int h, size_t step, int channels,
+                          const double* M, const double* v, const double* planes, int D, int radius, uint16_t* C,
+                          uint8_t* nvalid)
+{
+    std::vector<uint64_t> cen = census_all(ref, srcs, S, w, h, step, channels);
+    sweep_bands(cen.data(), S, w, h, M, v, planes, D, radius, [&](int x, int y, int d, int32_t c, int32_t nv) {
+        const size_t o = ((size_t)y * w + x) * D + d;
+        C[o] = (uint16_t)c;
+        nvalid[o] = (uint8_t)nv;
+    });
+}
+
+}  // namespace slamhip
+
+using namespace slamhip;
+
+extern "C" int slam_mvs_depth_host(const uint8_t* ref, const uint8_t* const* srcs, int S, int w, int h, size_t step,
+                                   int channels, const double* M, const double* v, const double* planes, int D,
+                                   int radius, int uniq, int min_views, int16_t* plane, int32_t* cost, float* inv_depth)
+{
+    if (!ref || !srcs || !plane || !cost || !inv_depth) return SLAM_E_INVALID_ARG;
+    if (int rc = mvs_check_args(S, w, h, channels, M, v, planes, D, radius, uniq, min_views)) return rc;
+    if (step < (size_t)w * channels) return SLAM_E_INVALID_ARG;
+    for (int s = 0; s < S; s++)
+        if (!srcs[s]) return SLAM_E_INVALID_ARG;
+
+    const size_t npx = (size_t)w * h;
+    std::vector<uint64_t> cen = census_all(ref, srcs, S, w, h, step, channels);
+    std::vector<MvsPixel> st(npx);
+    for (auto& p : st) mvs_pixel_init(p);
+    sweep_bands(cen.data(), S, w, h, M, v, planes, D, radius,
+                [&](int x, int y, int d, int32_t C, int32_t nv) { mvs_pixel_update(st[(size_t)y * w + x], d, C, nv); });
+    for (size_t i = 0; i < npx; i++) mvs_pixel_finish(st[i], planes, D, uniq, min_views, &plane[i], &cost[i], &inv_depth[i]);
     return SLAM_OK;
 }
+

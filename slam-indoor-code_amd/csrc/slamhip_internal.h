@@ -369,6 +369,12 @@ struct slam_ctx {
     slamhip::DevBuf mvs_census, mvs_par, mvs_mask, mvs_out, mvs_in;
     hipEvent_t mvs_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     double mvs_ms[4] = {0, 0, 0, 0};      // slam_mvs_last_timing: census, sweep, filter + count, emit
+    // semi-global aggregation (mvs_sgm.hip): the volume, the valid counts and S of one group of references,
+    // the scratch budget a group stays under (slam_mvs_sgm_set_budget; 0 = the default)
+    slamhip::DevBuf mvs_sgm;
+    hipEvent_t sgm_ev[3] = {nullptr, nullptr, nullptr};
+    double sgm_ms[3] = {0, 0, 0};         // slam_mvs_sgm_last_timing: volume, paths, winner
+    size_t sgm_budget = 0;
     // place recognition (place.hip): the assign partials of the K splits, the centroid norms, training's
     // words + distances + sorted order, its counts + starts + cursors + changed flag, the uploaded
     // offsets + weights, the staged buffers of the host-pointer calls
@@ -709,6 +715,19 @@ void jpeg_enc_release(slam_ctx* c);
 // ---- plane-sweep stereo (mvs.hip) ----
 // destroys the context's timing events
 void mvs_release(slam_ctx* c);
+// where a batch of references goes: the winner's three maps, or (C set) the cost volume itself
+struct MvsBatchOut {
+    int16_t* plane = nullptr;
+    int32_t* cost = nullptr;
+    float* inv = nullptr;
+    uint16_t* C = nullptr;
+    uint8_t* nvalid = nullptr;
+};
+// the body of slam_mvs_depth_batch_dev, shared with the volume's entry points (mvs_sgm.hip)
+int mvs_batch_run(slam_ctx* c, void* stream, const uint8_t* d_frames, int nframes, int w, int h, int channels, int nref,
+                  const int32_t* ref_idx, const int32_t* nsrc, const int32_t* src_idx, const double* M, const double* v,
+                  const double* planes, int D, int radius, int uniq, int min_views, const MvsBatchOut& out, bool check_only,
+                  double* ms);
 // ---- TSDF fusion and marching cubes (tsdf.hip, tsdf_host.cpp) ----
 // destroys the context's timing events
 void tsdf_release(slam_ctx* c);

@@ -34,8 +34,9 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
                   IMWRITE_JPEG_SAMPLING_FACTOR_420, IMWRITE_JPEG_SAMPLING_FACTOR_422, IMWRITE_JPEG_SAMPLING_FACTOR_444,
                   renderViews, renderCamera, renderStats,
                   censusTransform, planeSweepDepth, planeSweepDepthBatch, fuseDepthMaps,
+                  planeSweepCostVolume, sgmAggregate, planeSweepDepthSgm, planeSweepDepthSgmBatch, sgmLastTiming,
                   tsdfIntegrate, tsdfMesh, tsdfLastTiming)
-from .dense import DenseParams, densify, depth_maps, depth_planes, sweep_matrices
+from .dense import DenseParams, SgmParams, densify, depth_maps, depth_planes, sweep_matrices
 from . import surface
 from .surface import SurfaceParams, projection_matrix, volume_bounds
 from .place import Database, LoopParams, Vocabulary, detect_loops, verify_loop

@@ -231,6 +231,16 @@ SIGNATURES = {
     "slam_mvs_fuse": (_I, [_P, _P, _I, _I, _SZ, _I, _I, _P, _P, _P, _P, _P, _P, _P, _D, _I, _I, _I, _P, _P, _I, _P]),
     "slam_mvs_last_timing": (_I, [_P, _P]),
     "slam_mvs_depth_host": (_I, [_P, _P, _I, _I, _I, _SZ, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "slam_mvs_cost_volume_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "slam_mvs_sgm_aggregate_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "slam_mvs_depth_sgm_batch_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I,
+                                          _P, _P, _P]),
+    "slam_mvs_depth_sgm": (_I, [_P, _P, _P, _I, _I, _I, _SZ, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "slam_mvs_sgm_set_budget": (_I, [_P, _SZ]),
+    "slam_mvs_sgm_last_timing": (_I, [_P, _P]),
+    "slam_mvs_cost_volume_host": (_I, [_P, _P, _I, _I, _I, _SZ, _I, _P, _P, _P, _I, _I, _P, _P]),
+    "slam_mvs_sgm_aggregate_host": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "slam_mvs_depth_sgm_host": (_I, [_P, _P, _I, _I, _I, _SZ, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "slam_tsdf_integrate_dev": (_I, [_P, _P, _P, _I, _I, _I, _P, _D, _D, _P, _I, _I, _I, _I, _P, _P, _P, _I]),
     "slam_tsdf_mesh_dev": (_I, [_P, _P, _P, _I, _I, _I, _P, _D, _I, _P, _P, _P, _I, _I, _P, _P]),
     "slam_tsdf_integrate": (_I, [_P, _P, _I, _I, _I, _P, _D, _D, _P, _I, _I, _I, _I, _P, _P, _P, _I]),

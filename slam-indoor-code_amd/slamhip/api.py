@@ -1815,6 +1815,138 @@ def planeSweepDepthBatch(frames, ref_idx, src_idx, M, v, planes, radius=2, uniq=
     return plane, cost, inv
 
 
+# ---- semi-global aggregation of the sweep's cost volume ---------
+
+def _batch_args(ref_idx, src_idx, M, v, planes):
+    nref = len(ref_idx)
+    ref = np.ascontiguousarray(ref_idx, np.int32).reshape(nref)
+    nsrc = np.array([len(s) for s in src_idx], np.int32)
+    src = np.full((nref, 4), -1, np.int32)
+    for i, s in enumerate(src_idx):
+        if len(s) > 4:
+            raise ValueError("at most 4 sources per reference")
+        src[i, :len(s)] = s
+    M = np.ascontiguousarray(M, np.float64).reshape(nref, 36)
+    v = np.ascontiguousarray(v, np.float64).reshape(nref, 12)
+    planes = np.ascontiguousarray(planes, np.float64).reshape(nref, -1)
+    return nref, ref, nsrc, src, M, v, planes
+
+
+def planeSweepCostVolume(frames, ref_idx, src_idx, M, v, planes, radius=2, ctx=None, host=False):
+    """The cost volume the sweep never stores (slam_mvs_cost_volume_dev): (C uint16,
+    nvalid uint8), each (nref, h, w, D) with the plane index innermost, of the
+    references ref_idx among the frames; arguments as planeSweepDepthBatch.  frames:
+    a resident torch batch -> resident tensors; with host=True a list of host arrays
+    -> numpy arrays from the host twin, the same bits."""
+    nref, ref, nsrc, src, M, v, planes = _batch_args(ref_idx, src_idx, M, v, planes)
+    D = planes.shape[1]
+    if host:
+        fr, w, h, ch = _mvs_frames(list(frames))
+        C = np.empty((nref, h, w, D), np.uint16)
+        nv = np.empty((nref, h, w, D), np.uint8)
+        for i in range(nref):
+            S = int(nsrc[i])
+            sp = _ptr_array([fr[j] for j in src[i, :S]]) if S > 0 else None
+            check(lib().slam_mvs_cost_volume_host(ptr(fr[ref[i]]), sp, S, w, h, w * ch, ch, ptr(M[i]), ptr(v[i]),
+                                                  ptr(planes[i]), D, int(radius), ptr(C[i]), ptr(nv[i])))
+        return C, nv
+    import torch
+    c = _ctx(ctx)
+    fr, n, w, h, ch = _resident(frames)
+    C = torch.empty((nref, h, w, D), dtype=torch.uint16, device=fr.device)
+    nv = torch.empty((nref, h, w, D), dtype=torch.uint8, device=fr.device)
+    check(lib().slam_mvs_cost_volume_dev(c, None, ctypes.c_void_p(fr.data_ptr()), n, w, h, ch, nref, ptr(ref), ptr(nsrc),
+                                         ptr(src), ptr(M), ptr(v), ptr(planes), D, int(radius),
+                                         ctypes.c_void_p(C.data_ptr()), ctypes.c_void_p(nv.data_ptr())), c)
+    return C, nv
+
+
+def sgmAggregate(C, P1, P2, paths=8, ctx=None, host=False):
+    """Semi-global aggregation of given volumes (slam_mvs_sgm_aggregate_dev): C (n, h,
+    w, D) uint16 with every value <= 12544, the effective penalties 0 <= P1 <= P2 <=
+    65535 - 12544, paths 4 or 8 -> S (n, h, w, D) int32, the sum of the path costs.  A
+    resident torch tensor gives a resident tensor; a numpy array runs on the device
+    too unless host=True (the host twin, the same bits)."""
+    if isinstance(C, np.ndarray):
+        a = np.ascontiguousarray(C, np.uint16)
+        if a.ndim != 4:
+            raise ValueError("C: (n, h, w, D) uint16")
+        n, h, w, D = a.shape
+        S = np.empty(a.shape, np.int32)
+        if host:
+            check(lib().slam_mvs_sgm_aggregate_host(ptr(a), n, w, h, D, int(P1), int(P2), int(paths), ptr(S)))
+            return S
+        import torch
+        return sgmAggregate(torch.from_numpy(a.view(np.int16)).cuda().view(torch.uint16), P1, P2, paths, ctx=ctx).cpu().numpy()
+    import torch
+    if C.dtype != torch.uint16 or C.dim() != 4:
+        raise ValueError("C: (n, h, w, D) uint16")
+    c = _ctx(ctx)
+    C = C.contiguous()
+    torch.cuda.current_stream(C.device).synchronize()
+    n, h, w, D = C.shape
+    S = torch.empty((n, h, w, D), dtype=torch.int32, device=C.device)
+    check(lib().slam_mvs_sgm_aggregate_dev(c, None, ctypes.c_void_p(C.data_ptr()), n, w, h, D, int(P1), int(P2), int(paths),
+                                           ctypes.c_void_p(S.data_ptr())), c)
+    return S
+
+
+def planeSweepDepthSgm(ref, srcs, M, v, planes, radius=2, uniq=80, min_views=1, p1=10, p2=120, paths=8, ctx=None,
+                       host=False):
+    """planeSweepDepth with semi-global aggregation between the volume and the winner
+    (slam_mvs_depth_sgm, host=True: slam_mvs_depth_sgm_host, the same bits).  p1 <= p2
+    in 0..255 are the penalties per window pixel and source in Hamming bits for a
+    change of one plane and of more; paths 4 or 8.  cost is S[best]."""
+    fr, w, h, ch = _mvs_frames([ref] + list(srcs))
+    S = len(fr) - 1
+    M, v, planes = _mvs_pose_args(M, v, planes, S) if S > 0 else (np.zeros((0, 9)), np.zeros((0, 3)),
+                                                                  np.ascontiguousarray(planes, np.float64).reshape(-1))
+    plane = np.empty((h, w), np.int16)
+    cost = np.empty((h, w), np.int32)
+    inv = np.empty((h, w), np.float32)
+    sp = _ptr_array(fr[1:]) if S > 0 else None
+    tail = (S, w, h, w * ch, ch, ptr(M), ptr(v), ptr(planes), len(planes), int(radius), int(uniq), int(min_views),
+            int(p1), int(p2), int(paths), ptr(plane), ptr(cost), ptr(inv))
+    if host:
+        check(lib().slam_mvs_depth_sgm_host(ptr(fr[0]), sp, *tail))
+    else:
+        c = _ctx(ctx)
+        check(lib().slam_mvs_depth_sgm(c, ptr(fr[0]), sp, *tail), c)
+    return plane, cost, inv
+
+
+def planeSweepDepthSgmBatch(frames, ref_idx, src_idx, M, v, planes, radius=2, uniq=80, min_views=1, p1=10, p2=120, paths=8,
+                            ctx=None, budget=None):
+    """planeSweepDepthBatch with semi-global aggregation (slam_mvs_depth_sgm_batch_dev).
+    The references are worked through in groups whose scratch stays under `budget`
+    bytes (None: the library's 8 GiB); the results do not depend on it."""
+    import torch
+    c = _ctx(ctx)
+    fr, n, w, h, ch = _resident(frames)
+    nref, ref, nsrc, src, M, v, planes = _batch_args(ref_idx, src_idx, M, v, planes)
+    plane = torch.empty((nref, h, w), dtype=torch.int16, device=fr.device)
+    cost = torch.empty((nref, h, w), dtype=torch.int32, device=fr.device)
+    inv = torch.empty((nref, h, w), dtype=torch.float32, device=fr.device)
+    check(lib().slam_mvs_sgm_set_budget(c, int(budget or 0)), c)
+    try:
+        check(lib().slam_mvs_depth_sgm_batch_dev(c, None, ctypes.c_void_p(fr.data_ptr()), n, w, h, ch, nref, ptr(ref),
+                                                 ptr(nsrc), ptr(src), ptr(M), ptr(v), ptr(planes), planes.shape[1],
+                                                 int(radius), int(uniq), int(min_views), int(p1), int(p2), int(paths),
+                                                 ctypes.c_void_p(plane.data_ptr()), ctypes.c_void_p(cost.data_ptr()),
+                                                 ctypes.c_void_p(inv.data_ptr())), c)
+    finally:
+        lib().slam_mvs_sgm_set_budget(c, 0)
+    return plane, cost, inv
+
+
+def sgmLastTiming(ctx=None):
+    """HIP-event times of the context's last aggregated sweep: dict(volume_ms, paths_ms, winner_ms)"""
+    ms = np.zeros(3, np.float64)
+    c = _ctx(ctx)
+    check(lib().slam_mvs_sgm_last_timing(c, ptr(ms)), c)
+    return dict(zip(("volume_ms", "paths_ms", "winner_ms"), ms.tolist()))
+
+
 def fuseDepthMaps(frames, inv_depth, nbrs, M, v, B, c, eps=0.01, min_consistent=1, step=4, radius=2, frame_idx=None,
                   cap=None, ctx=None):
     """slam_mvs_fuse_dev / slam_mvs_fuse: the pairwise consistency filter over nmaps

@@ -67,13 +67,30 @@ def depth_planes(K, R, t, sparse_points, shape, D):
     return w0 * (1.0 - t) + w1 * t          # both ends exact
 
 
+class SgmParams:
+    """Semi-global aggregation of the sweep's cost volume: the
+    penalties p1 <= p2 (0..255, Hamming bits per window pixel and source) for a change
+    of one plane and of more between neighbouring pixels, and 4 or 8 paths.  The
+    defaults are the customary census penalties of GPU SGM libraries; they are not
+    tuned on this project's data."""
+
+    def __init__(self, p1=10, p2=120, paths=8):
+        if not 0 <= p1 <= p2 <= 255 or paths not in (4, 8):
+            raise ValueError("SgmParams: 0 <= p1 <= p2 <= 255, paths 4 or 8")
+        self.p1, self.p2, self.paths = int(p1), int(p2), int(paths)
+
+
 class DenseParams:
     """slam_main(dense=...) / densify: D planes per reference, `sources` nearest good
     frames per reference, the aggregation radius, the uniqueness ratio in percent,
     the least number of sources that must see the winner, and the fuse step's eps,
-    min_consistent and grid step."""
+    min_consistent and grid step.  sgm (an SgmParams; None = winner-take-all, every
+    byte as without it) aggregates the cost volume semi-globally before the winner."""
 
-    def __init__(self, D=64, sources=2, radius=2, uniq=80, min_views=1, eps=0.01, min_consistent=1, step=4):
+    def __init__(self, D=64, sources=2, radius=2, uniq=80, min_views=1, eps=0.01, min_consistent=1, step=4, sgm=None):
+        if sgm is not None and not isinstance(sgm, SgmParams):
+            raise ValueError("DenseParams: sgm is an SgmParams or None")
+        self.sgm = sgm
         if not 4 <= D <= 256 or not 1 <= sources <= MAX_SOURCES or not 0 <= radius <= 3 or not 1 <= uniq <= 100 \
                 or not 1 <= min_views <= sources or not eps >= 0 or not 0 <= min_consistent <= MAX_SOURCES or step < 1:
             raise ValueError("DenseParams: D 4..256, sources 1..4, radius 0..3, uniq 1..100, min_views 1..sources, "
@@ -184,7 +201,8 @@ def depth_maps(frames, K, rotations, positions, sparse_points, params=None, ctx=
     """The plane-sweep depth map of every reference of a sequence: (plan, inv_depth),
     with plan as plan() returns it and inv_depth[m] the float32 (h, w) map of frame
     plan["ref"][m]: a list of host arrays with host=True (slam_mvs_depth_host), else one
-    resident (nref, h, w) tensor.  None when there are fewer than two frames or no
+    resident (nref, h, w) tensor.  With params.sgm the maps are the semi-globally
+    aggregated ones (slam_mvs_depth_sgm_batch_dev / slam_mvs_depth_sgm_host).  None when there are fewer than two frames or no
     reference.  densify and surface.reconstruct both start here."""
     from . import api
     params = params or DenseParams()
@@ -201,19 +219,28 @@ def depth_maps(frames, K, rotations, positions, sparse_points, params=None, ctx=
         return None
     h, w = shape[0], shape[1]
     st = stage_frames(frames, host)
+    sgm = params.sgm
     if host:
         inv = []
         for m, i in enumerate(P["ref"]):
             S = len(P["src"][m])
-            inv.append(api.planeSweepDepth(st[i], [st[j] for j in P["src"][m]], P["M"][m, :S], P["v"][m, :S], P["planes"][m],
-                                           params.radius, params.uniq, params.min_views, host=True)[2])
+            args = (st[i], [st[j] for j in P["src"][m]], P["M"][m, :S], P["v"][m, :S], P["planes"][m], params.radius,
+                    params.uniq, params.min_views)
+            if sgm is None:
+                inv.append(api.planeSweepDepth(*args, host=True)[2])
+            else:
+                inv.append(api.planeSweepDepthSgm(*args, sgm.p1, sgm.p2, sgm.paths, host=True)[2])
         return P, inv
     import torch
     inv = torch.empty((nr, h, w), dtype=torch.float32, device=st.device)
     for m0 in range(0, nr, chunk):
         m1 = min(nr, m0 + chunk)
-        _, _, iv = api.planeSweepDepthBatch(st, P["ref"][m0:m1], P["src"][m0:m1], P["M"][m0:m1], P["v"][m0:m1],
-                                            P["planes"][m0:m1], params.radius, params.uniq, params.min_views, ctx=ctx)
+        args = (st, P["ref"][m0:m1], P["src"][m0:m1], P["M"][m0:m1], P["v"][m0:m1], P["planes"][m0:m1], params.radius,
+                params.uniq, params.min_views)
+        if sgm is None:
+            _, _, iv = api.planeSweepDepthBatch(*args, ctx=ctx)
+        else:
+            _, _, iv = api.planeSweepDepthSgmBatch(*args, sgm.p1, sgm.p2, sgm.paths, ctx=ctx)
         inv[m0:m1] = iv
     return P, inv
 
