@@ -1342,6 +1342,85 @@ int slam_tsdf_mesh_host(const int32_t* volume, int nx, int ny, int nz, const dou
  * nothing was emitted); 0 before the first call. */
 int slam_tsdf_last_timing(slam_ctx* ctx, double* ms);
 
+/* ---- texture of the fused surface: a per-face atlas from the keyframes (tex.hip) ---- */
+/* An opt-in stage after the surface.  The definition of every
+ * value is tests/tex_ref.py; the device and the host twins equal it bit for bit.  The
+ * reference has no such stage.  The mesh is slam_tsdf_mesh's: V nv x 3 f64, C nv x 3 u8
+ * (blue, green, red), F nf x 3 int32.  A view is a frame and its projection P (3 x 4
+ * row-major f64, mathematically K [R | t], pixel centres at integer coordinates).
+ *
+ * slam_tex_select_dev: d_ids are nv id images (nv x h x w int32, device) as
+ * slam_render_views_dev writes them for the mesh seen from nv views.  count[m][f] = the
+ * pixels of image m whose kind is 2 (face) and whose index is f < nf; everything else
+ * (the background -1, points, lines, indices >= nf) is ignored.  The caller owns the
+ * state d_best_count / d_best_view (nf int32 each, device), initially 0 / -1; the
+ * views are folded in with their global index view0 + m: a view with count c replaces
+ * the state iff c > best_count or (c == best_count and c > 0 and its index < best_view).
+ * All of it is integer, so the state after a set of views does not depend on how they
+ * are split over calls nor on the calls' order.  nf > 2^30: SLAM_E_UNSUPPORTED; nv, nf
+ * or view0 < 0, view0 + nv > 2^31 - 1, h or w < 1, h w > 2^30, a null pointer with a
+ * non-zero count: SLAM_E_INVALID_ARG.  nv == 0 or nf == 0: SLAM_OK, no launch.
+ * Synchronous. */
+int slam_tex_select_dev(slam_ctx* ctx, void* stream, const int32_t* d_ids, int nv, int h, int w, int view0, int nf,
+                        int32_t* d_best_count, int32_t* d_best_view);
+/* The atlas layout, a pure function of (nf, T, page); host only.  T (1..64) is the
+ * texels per triangle leg, S = T + 4 the cell size, cells_x = page / S with page in
+ * S..8192.  Face f lives in cell f >> 1, half f & 1; cells are in raster order,
+ * cells_x per row and cells_x rows per page.  Every page is *page_w = cells_x S texels
+ * wide; page p is S x (the cell rows it uses) high.  In cell-local texel coordinates
+ * (texel (i, j) has its centre at (i + 0.5, j + 0.5)) half 0 maps the corners a, b, c to
+ * (1, 1), (1 + T, 1), (1, 1 + T), half 1 to (T + 3, T + 3), (3, T + 3), (T + 3, 3);
+ * texel (i, j) belongs to half 0 iff i + j <= T + 2.  Outputs, each nullable: page_h
+ * (cap_pages int32; *npages > cap_pages: SLAM_E_CAPACITY, *npages and *page_w are set),
+ * uv (nf x 3 x 2 f64: (x / page_w, 1 - y / page_h) of a corner at page texel (x, y)),
+ * face_page (nf int32).  nf == 0: zero pages.  T or page out of range, nf < 0:
+ * SLAM_E_INVALID_ARG; nf > 2^30: SLAM_E_UNSUPPORTED. */
+int slam_tex_layout(int nf, int T, int page, int* npages, int* page_w, int32_t* page_h, int cap_pages, double* uv,
+                    int32_t* face_page);
+/* Fills the atlas: d_atlas holds the pages one after the other, each page_h x page_w x 3
+ * u8 (blue, green, red), exactly the sum of slam_tex_layout's page sizes.  frames: n
+ * resident frames of h x w x channels (1 or 3) bytes; view m is frame frame_idx[m] (host;
+ * NULL: m itself) with the projection P[m] (host, nviews x 12).  Per texel: (0, 0, 0)
+ * when its owner half's face is >= nf.  Otherwise, with (x', y') its centre in the cell,
+ * half 0: beta = (x' - 1) / T, gamma = (y' - 1) / T; half 1: beta = (T + 3 - x') / T,
+ * gamma = (T + 3 - y') / T; alpha = (1 - beta) - gamma; X = (alpha Va + beta Vb) + gamma
+ * Vc per component (f64, this order, no contraction).  If best_count[f] >= min_pixels
+ * and best_view[f] >= 0: h_i = ((P[i][0] X + P[i][1] Y) + P[i][2] Z) + P[i][3] of the
+ * best view; h_2 > 0 and u = h_0 / h_2, v = h_1 / h_2 finite are required; u is clamped
+ * to [0, w - 1], v to [0, h - 1]; x0 = floor(u), x1 = min(x0 + 1, w - 1), wx =
+ * (int)floor((u - x0) 256 + 0.5), y alike; per channel top = p00 (256 - wx) + p01 wx, bot
+ * alike, value = (top (256 - wy) + bot wy + 32768) >> 16; a gray frame fills the three
+ * channels alike.  Any failed test takes the Gouraud fallback per channel:
+ * (uint8)clamp(floor(((alpha ca + beta cb) + gamma cc) + 0.5), 0, 255) of the vertex
+ * colours.  A NaN or an infinity in P, V or the projection fails a test and never
+ * reaches an integer conversion.  SLAM_E_INVALID_ARG: T outside 1..64, page outside
+ * T + 4..8192, min_pixels outside 1..2^30, a face index outside nv, a best view outside
+ * -1..nviews - 1, a frame index outside n, channels other than 1 or 3, nviews outside
+ * 0..2^20, a null pointer with a non-zero count; nf > 2^30 (or more than 2^39 texels):
+ * SLAM_E_UNSUPPORTED; nothing is filled then.  nf == 0: SLAM_OK, nothing written.
+ * Synchronous. */
+int slam_tex_fill_dev(slam_ctx* ctx, void* stream, const double* d_V, const uint8_t* d_C, const int32_t* d_F, int nv, int nf,
+                      const uint8_t* d_frames, int n, int h, int w, int channels, const int32_t* frame_idx, const double* P,
+                      int nviews, const int32_t* d_best_count, const int32_t* d_best_view, int min_pixels, int T, int page,
+                      uint8_t* d_atlas);
+/* slam_tex_select_dev / slam_tex_fill_dev for ids, state, mesh, frames and atlas in host
+ * memory; the state is updated in place. */
+int slam_tex_select(slam_ctx* ctx, const int32_t* ids, int nv, int h, int w, int view0, int nf, int32_t* best_count,
+                    int32_t* best_view);
+int slam_tex_fill(slam_ctx* ctx, const double* V, const uint8_t* C, const int32_t* F, int nv, int nf, const uint8_t* frames,
+                  int n, int h, int w, int channels, const int32_t* frame_idx, const double* P, int nviews,
+                  const int32_t* best_count, const int32_t* best_view, int min_pixels, int T, int page, uint8_t* atlas);
+/* The host twins: no context, no device, the same arithmetic (csrc/tex_math.h) on up to
+ * 16 threads, the same results and error codes bit for bit. */
+int slam_tex_select_host(const int32_t* ids, int nv, int h, int w, int view0, int nf, int32_t* best_count, int32_t* best_view);
+int slam_tex_fill_host(const double* V, const uint8_t* C, const int32_t* F, int nv, int nf, const uint8_t* frames, int n, int h,
+                       int w, int channels, const int32_t* frame_idx, const double* P, int nviews, const int32_t* best_count,
+                       const int32_t* best_view, int min_pixels, int T, int page, uint8_t* atlas);
+/* Library HIP-event times (ms) of the context's last slam_tex_select_dev (ms[0]:
+ * tex_count + tex_best over all its chunks) and of its last slam_tex_fill_dev (ms[1]:
+ * tex_fill); 0 before the first call and when nothing was launched. */
+int slam_tex_last_timing(slam_ctx* ctx, double* ms);
+
 /* ---- place recognition: a flat visual vocabulary and bag-of-words retrieval (place.hip) ----
  * All arithmetic is integer except the one IEEE division of a score, so device,
  * host twin and the numpy contract (tests/place_ref.py) agree bit for bit.

@@ -430,7 +430,7 @@ void slam_destroy(slam_ctx* c)
                       &c->mvs_census, &c->mvs_par, &c->mvs_mask, &c->mvs_out, &c->mvs_in, &c->mvs_sgm,
                       &c->place_part, &c->place_norm, &c->place_word, &c->place_cnt, &c->place_par, &c->place_in,
                       &c->loop_ws, &c->loop_in, &c->loop_pgo, &c->gba_ws, &c->gba_in,
-                      &c->tsdf_par, &c->tsdf_ws, &c->tsdf_in};
+                      &c->tsdf_par, &c->tsdf_ws, &c->tsdf_in, &c->tex_ws, &c->tex_par, &c->tex_in};
     for (DevBuf* b : bufs) b->release();
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->ev_up) (void)hipEventDestroy(c->ev_up);
@@ -447,6 +447,7 @@ void slam_destroy(slam_ctx* c)
     render_release(c);
     mvs_release(c);
     tsdf_release(c);
+    tex_release(c);
     for (auto& f : c->prof)
         for (hipEvent_t e : f.ev) (void)hipEventDestroy(e);
     if (c->ev_sync) (void)hipEventDestroy(c->ev_sync);

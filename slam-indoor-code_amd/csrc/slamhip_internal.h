@@ -391,6 +391,11 @@ struct slam_ctx {
     slamhip::DevBuf tsdf_par, tsdf_ws, tsdf_in;
     hipEvent_t tsdf_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     double tsdf_ms[4] = {0, 0, 0, 0};     // slam_tsdf_last_timing: integrate, classify + count, scan, emit
+    // texture atlas (tex.hip): the per-face counts of one chunk of views, the per-view parameter block
+    // and the check flag of a fill, the staged buffers of the host-pointer calls
+    slamhip::DevBuf tex_ws, tex_par, tex_in;
+    hipEvent_t tex_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    double tex_ms[2] = {0, 0};            // slam_tex_last_timing: count + best, fill
 
     bool prof_on = false;
     slamhip::ProfFamily prof[slamhip::kProfFamilies];
@@ -735,6 +740,17 @@ void tsdf_release(slam_ctx* c);
 int tsdf_check_volume(const void* volume, int nx, int ny, int nz, const double* origin, double voxel);
 int tsdf_check_maps(double trunc, const void* frames, int nframes, int w, int h, int channels, const int32_t* frame_idx,
                     const void* inv_depth, const double* P, int nmaps);
+// ---- texture atlas (tex.hip, tex_host.cpp) ----
+struct TexView;
+// destroys the context's timing events
+void tex_release(slam_ctx* c);
+// argument checks shared by the device entry points and the host twins (tex_host.cpp)
+int tex_check_select(const void* ids, int nv, int h, int w, int view0, int nf, const void* best_count, const void* best_view);
+int tex_check_fill(const void* V, const void* C, const void* F, int nv, int nf, const void* frames, int n, int h, int w,
+                   int channels, const int32_t* frame_idx, const double* P, int nviews, const void* best_count,
+                   const void* best_view, int min_pixels, int T, int page, const void* atlas);
+// the views' parameter block from P (nviews x 12) and the frame indices (NULL: the identity)
+void tex_make_views(const double* P, const int32_t* frame_idx, int nviews, TexView* out);
 // ---- place recognition (place.hip, place_host.cpp) ----
 // argument checks shared by the device entry points and the host twins (place_host.cpp)
 int place_check_assign(const void* desc, int n, const void* cent, int K, int kind);

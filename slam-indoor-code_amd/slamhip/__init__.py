@@ -35,10 +35,11 @@ from .api import (Context, GlobalData, MatcherTypeError, TemporalImageData, ba_r
                   renderViews, renderCamera, renderStats,
                   censusTransform, planeSweepDepth, planeSweepDepthBatch, fuseDepthMaps,
                   planeSweepCostVolume, sgmAggregate, planeSweepDepthSgm, planeSweepDepthSgmBatch, sgmLastTiming,
-                  tsdfIntegrate, tsdfMesh, tsdfLastTiming)
+                  tsdfIntegrate, tsdfMesh, tsdfLastTiming,
+                  texSelect, texLayout, texFill, texLastTiming)
 from .dense import DenseParams, SgmParams, densify, depth_maps, depth_planes, sweep_matrices
 from . import surface
-from .surface import SurfaceParams, projection_matrix, volume_bounds
+from .surface import SurfaceParams, TextureParams, projection_matrix, volume_bounds
 from .place import Database, LoopParams, Vocabulary, detect_loops, verify_loop
 from . import place
 from . import loopclose

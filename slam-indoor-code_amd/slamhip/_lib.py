@@ -248,6 +248,14 @@ SIGNATURES = {
     "slam_tsdf_integrate_host": (_I, [_P, _I, _I, _I, _P, _D, _D, _P, _I, _I, _I, _I, _P, _P, _P, _I]),
     "slam_tsdf_mesh_host": (_I, [_P, _I, _I, _I, _P, _D, _I, _P, _P, _P, _I, _I, _P, _P]),
     "slam_tsdf_last_timing": (_I, [_P, _P]),
+    "slam_tex_select_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "slam_tex_layout": (_I, [_I, _I, _I, _P, _P, _P, _I, _P, _P]),
+    "slam_tex_fill_dev": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
+    "slam_tex_select": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "slam_tex_fill": (_I, [_P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
+    "slam_tex_select_host": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "slam_tex_fill_host": (_I, [_P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
+    "slam_tex_last_timing": (_I, [_P, _P]),
     "slam_voc_assign_dev": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P]),
     "slam_voc_train_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "slam_bow_vectors_dev": (_I, [_P, _P, _P, _P, _I, _P, _I, _P, _P]),

@@ -2120,3 +2120,152 @@ def tsdfLastTiming(ctx=None):
     c = _ctx(ctx)
     check(lib().slam_tsdf_last_timing(c, ptr(ms)), c)
     return dict(zip(("integrate", "classify_count", "scan", "emit"), [float(x) for x in ms]))
+
+
+# ---- texture of the fused surface: a per-face atlas ----
+
+def _is_resident(a):
+    return not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
+
+
+def _dptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+
+def texSelect(ids, view0, nf, state=None, ctx=None, host=False):
+    """slam_tex_select_dev / slam_tex_select / slam_tex_select_host: fold the id images `ids`
+    (nv, h, w) int32 (renderViews(..., ids=True) of the mesh from nv views) into the per-face
+    state (best_count, best_view), two int32 arrays of nf, updated in place and returned.
+    The views' global indices are view0 .. view0 + nv - 1; state=None starts from (0, -1).
+    Resident ids take (and give) resident state tensors; host ids go through the device or,
+    with host=True, through the host twin: the same bits without a device."""
+    nf = int(nf)
+    if _is_resident(ids):
+        import torch
+        if host:
+            raise ValueError("host=True takes host ids")
+        if ids.dtype != torch.int32 or ids.dim() != 3:
+            raise ValueError("ids: int32 (nv, h, w)")
+        ids = ids.contiguous()
+        if state is None:
+            state = (torch.zeros(nf, dtype=torch.int32, device=ids.device), torch.full((nf,), -1, dtype=torch.int32, device=ids.device))
+        bc, bv = state
+        if any(t.dtype != torch.int32 or tuple(t.shape) != (nf,) or not t.is_contiguous() or t.device != ids.device for t in (bc, bv)):
+            raise ValueError("state: two contiguous int32 tensors of nf on the ids' device")
+        torch.cuda.current_stream(ids.device).synchronize()
+        h_ctx = _ctx(ctx)
+        check(lib().slam_tex_select_dev(h_ctx, None, _dptr(ids), int(ids.shape[0]), int(ids.shape[1]), int(ids.shape[2]), int(view0),
+                                        nf, _dptr(bc), _dptr(bv)), h_ctx)
+        return bc, bv
+    ids = np.ascontiguousarray(ids, np.int32)
+    if ids.ndim != 3:
+        raise ValueError("ids: int32 (nv, h, w)")
+    if state is None:
+        state = (np.zeros(nf, np.int32), np.full(nf, -1, np.int32))
+    bc, bv = state
+    if any(not isinstance(a, np.ndarray) or a.dtype != np.int32 or a.shape != (nf,) or not a.flags.c_contiguous for a in (bc, bv)):
+        raise ValueError("state: two contiguous int32 arrays of nf")
+    tail = (ptr(ids) if ids.size else None, ids.shape[0], ids.shape[1], ids.shape[2], int(view0), nf, ptr(bc) if nf else None,
+            ptr(bv) if nf else None)
+    if host:
+        check(lib().slam_tex_select_host(*tail))
+    else:
+        h_ctx = _ctx(ctx)
+        check(lib().slam_tex_select(h_ctx, *tail), h_ctx)
+    return bc, bv
+
+
+def texLayout(nf, T, page):
+    """slam_tex_layout: the atlas layout of nf faces with T texels per triangle leg on pages
+    of at most `page` texels -> (page_w, page_h (list, one per page), uv (nf, 3, 2) float64,
+    page (nf,) int32).  A corner at page texel (x, y) has uv (x / page_w, 1 - y / page_h)."""
+    nf = int(nf)
+    npages, pw = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().slam_tex_layout(nf, int(T), int(page), ctypes.byref(npages), ctypes.byref(pw), None, 0, None, None))
+    ph = np.zeros(max(npages.value, 1), np.int32)
+    uv = np.zeros((max(nf, 1), 3, 2), np.float64)
+    fp = np.zeros(max(nf, 1), np.int32)
+    check(lib().slam_tex_layout(nf, int(T), int(page), ctypes.byref(npages), ctypes.byref(pw), ptr(ph), npages.value,
+                                ptr(uv) if nf else None, ptr(fp) if nf else None))
+    return pw.value, [int(v) for v in ph[:npages.value]], uv[:nf], fp[:nf]
+
+
+def _split_pages(atlas, page_w, page_h):
+    out, o = [], 0
+    for hgt in page_h:
+        out.append(atlas[o:o + hgt * page_w * 3].reshape(hgt, page_w, 3))
+        o += hgt * page_w * 3
+    return out
+
+
+def texFill(vertices, colors, faces, frames, P, best_count, best_view, min_pixels=4, T=12, page=4096, frame_idx=None, ctx=None,
+            host=False):
+    """slam_tex_fill_dev / slam_tex_fill / slam_tex_fill_host: the atlas pages (a list of
+    (page_h, page_w, 3) uint8 arrays, blue-green-red) of the mesh vertices (nv, 3) float64,
+    colors (nv, 3) uint8, faces (nf, 3) int32.  View m is frame frame_idx[m] (default m) with the
+    projection P[m] (3 x 4, surface.projection_matrix); best_count / best_view are texSelect's
+    state.  A resident frame batch (n, h, w[, 3]) takes the mesh and the state as host arrays or
+    resident tensors; host frames (a list or an array) go through the device or, with host=True,
+    through the host twin: the same bits without a device."""
+    P = np.ascontiguousarray(P, np.float64).reshape(-1, 12)
+    nviews = len(P)
+    fi = None if frame_idx is None else np.ascontiguousarray(frame_idx, np.int32).reshape(nviews)
+    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
+    pw, ph, _, _ = texLayout(nf, T, page)
+    nbytes = sum(ph) * pw * 3
+    scal = (int(min_pixels), int(T), int(page))
+    if _is_resident(frames):
+        import torch
+        if host:
+            raise ValueError("host=True takes host frames")
+        fr, n, w, h, ch = _resident(frames)
+        dev = fr.device
+
+        def put(a, dt, shape):
+            if not _is_resident(a):
+                a = torch.from_numpy(np.ascontiguousarray(a, dt).reshape(shape)).to(dev)
+            if a.dtype != getattr(torch, np.dtype(dt).name) or tuple(a.shape) != shape or a.device != dev:
+                raise ValueError(f"expected {np.dtype(dt).name} {shape} on the frames' device")
+            return a.contiguous()
+
+        V, C, F = put(vertices, np.float64, (nv, 3)), put(colors, np.uint8, (nv, 3)), put(faces, np.int32, (nf, 3))
+        bc, bv = put(best_count, np.int32, (nf,)), put(best_view, np.int32, (nf,))
+        atlas = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        h_ctx = _ctx(ctx)
+        check(lib().slam_tex_fill_dev(h_ctx, None, _dptr(V), _dptr(C), _dptr(F), nv, nf, _dptr(fr), n, h, w, ch, ptr(fi), ptr(P),
+                                      nviews, _dptr(bc), _dptr(bv), *scal, _dptr(atlas) if nbytes else None), h_ctx)
+        return _split_pages(atlas[:nbytes].cpu().numpy(), pw, ph)
+    frames = list(frames)
+    if frames:
+        fl, w, h, ch = _mvs_frames(frames)
+        fr = np.ascontiguousarray(np.stack(fl))
+    else:
+        fl, w, h, ch, fr = [], 1, 1, 1, None
+    V = np.ascontiguousarray(vertices, np.float64).reshape(nv, 3)
+    C = np.ascontiguousarray(colors, np.uint8).reshape(nv, 3)
+    F = np.ascontiguousarray(faces, np.int32).reshape(nf, 3)
+    bc = np.ascontiguousarray(best_count, np.int32).reshape(nf)
+    bv = np.ascontiguousarray(best_view, np.int32).reshape(nf)
+    atlas = np.zeros(max(nbytes, 1), np.uint8)
+
+    def p0(a):
+        return ptr(a) if a is not None and a.size else None
+
+    tail = (p0(V), p0(C), p0(F), nv, nf, p0(fr), len(fl), h, w, ch, ptr(fi), p0(P), nviews, p0(bc), p0(bv), *scal,
+            ptr(atlas) if nbytes else None)
+    if host:
+        check(lib().slam_tex_fill_host(*tail))
+    else:
+        h_ctx = _ctx(ctx)
+        check(lib().slam_tex_fill(h_ctx, *tail), h_ctx)
+    return _split_pages(atlas[:nbytes], pw, ph)
+
+
+def texLastTiming(ctx=None):
+    """slam_tex_last_timing: library HIP-event milliseconds of the last texSelect on the device
+    (tex_count + tex_best) and of the last texFill: dict(select, fill)"""
+    ms = np.zeros(2, np.float64)
+    c = _ctx(ctx)
+    check(lib().slam_tex_last_timing(c, ptr(ms)), c)
+    return dict(zip(("select", "fill"), [float(x) for x in ms]))

@@ -1540,7 +1540,11 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
     by marching cubes (surface.fuse_maps); the mesh goes to gd.surfaceVertices /
     gd.surfaceColors / gd.surfaceFaces and, with out_dir, to surface.ply in
     scene.write_mesh's format.  Every other file is byte-identical with and without it.
-    Without dense it raises ValueError.
+    Without dense it raises ValueError.  With surface.texture (a surface.TextureParams)
+    the mesh is also textured from the good frames (surface.texture, DESIGN.md section
+    29): gd.surfaceTexture and, with out_dir, surface.obj, surface.mtl and
+    surface_atlas_<p>.png (scene.write_textured_mesh); surface.ply and every other file
+    stay byte-identical.
 
     loops (opt-in; a place.LoopParams, None keeps, computes and writes nothing): the
     good frames are kept as for dense (both may be set), and after the last cycle
@@ -1651,6 +1655,14 @@ def slam_main(media, K, cfg, ops=None, out_dir=None, stats=None, dist=None, newK
             if logs.out_dir:
                 from .scene import Mesh, write_mesh
                 write_mesh(res[0], res[1], [Mesh(res[2], res[2])], os.path.join(logs.out_dir, "surface.ply"))
+            if surface.texture is not None:
+                # the good frames are still resident: every one of them is a view of the mesh
+                gd.surfaceTexture = surface_mod.texture(res[0], res[1], res[2], staged if staged is not None else logs.frames, K,
+                                                        gd.cameraRotations, gd.spatialCameraPositions, surface.texture, ctx=dctx)
+                if logs.out_dir:
+                    from .scene import write_textured_mesh
+                    tx = gd.surfaceTexture
+                    write_textured_mesh(os.path.join(logs.out_dir, "surface.obj"), res[0], res[2], tx.uv, tx.page, tx.atlas, ctx=dctx)
         if logs.out_dir:
             with open(os.path.join(logs.out_dir, "dense_points.txt"), "w") as f:
                 if len(gd.densePoints):

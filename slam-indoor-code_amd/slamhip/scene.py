@@ -18,6 +18,8 @@ files (src/main.cpp:55-71).
   render             the window's picture: cloud, trajectory and meshes through
                      api.renderViews, seen with viz::Camera(Vec2d(1, 1), Size(1000, 1000))
   write_ppm / write_png   the frames on disk
+  write_textured_mesh / load_textured_mesh   the textured surface (surface.texture, DESIGN.md
+                     section 29) as Wavefront OBJ + MTL + one image per atlas page
   main               the onlyViz branch of main()
 
 The numeric steps are slamhip.api's clusterizePoints / getBestFittingPlaneByPoints
@@ -356,6 +358,126 @@ def write_image(path, frame, ctx=None):
             raise OSError(f"cannot write {path}")
     else:
         (write_ppm if name.endswith(".ppm") else write_png)(path, frame)
+
+
+def read_image(path, ctx=None):
+    """write_image's own files back as (h, w, 3) uint8 blue-green-red: a PNG as write_png writes it
+    (8-bit RGB, filter 0 on every row), a binary PPM, or a JPEG through api.imread"""
+    name = path.lower()
+    if name.endswith((".jpg", ".jpeg")):
+        return np.asarray(api.imread(path, ctx=ctx))
+    with open(path, "rb") as f:
+        data = f.read()
+    if name.endswith(".ppm"):
+        head = data.split(b"\n", 3)
+        if len(head) != 4 or head[0] != b"P6" or head[2] != b"255":
+            raise ValueError(f"{path}: not a PPM written by write_ppm")
+        w, h = (int(v) for v in head[1].split())
+        return np.ascontiguousarray(np.frombuffer(head[3], np.uint8, h * w * 3).reshape(h, w, 3)[:, :, ::-1])
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError(f"{path}: not a PNG")
+    o, idat, w, h = 8, b"", 0, 0
+    while o + 8 <= len(data):
+        n, kind = struct.unpack(">I", data[o:o + 4])[0], data[o + 4:o + 8]
+        body = data[o + 8:o + 8 + n]
+        if kind == b"IHDR":
+            w, h, depth, colour, _, _, interlace = struct.unpack(">IIBBBBB", body)
+            if (depth, colour, interlace) != (8, 2, 0):
+                raise ValueError(f"{path}: not a PNG written by write_png")
+        elif kind == b"IDAT":
+            idat += body
+        o += 12 + n
+    rows = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(h, 1 + 3 * w)
+    if rows[:, 0].any():
+        raise ValueError(f"{path}: a filtered row; not a PNG written by write_png")
+    return np.ascontiguousarray(rows[:, 1:].reshape(h, w, 3)[:, :, ::-1])
+
+
+def write_textured_mesh(path, vertices, faces, uv, page, atlases, atlas_ext=".png", ctx=None):
+    """A textured mesh as Wavefront OBJ + MTL + one image per atlas page: `path` (x.obj), x.mtl and
+    x_atlas_<p><atlas_ext> beside it, the images through write_image.  vertices (n, 3) are written as
+    float32 (as write_mesh does), uv (nf, 3, 2) as exact `repr` floats, three `vt` per face in face
+    order; faces (nf, 3) index the vertices, page (nf,) names each face's atlas page (material
+    page_<p>).  PNG is the default: a 4:2:0 JPEG would bleed chroma across the atlas cells.
+    Returns the files written."""
+    pts = np.ascontiguousarray(vertices, np.float64).astype(np.float32).reshape(-1, 3)
+    fcs = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    uv = np.ascontiguousarray(uv, np.float64).reshape(-1, 3, 2)
+    page = np.ascontiguousarray(page, np.int32).reshape(-1)
+    if len(uv) != len(fcs) or len(page) != len(fcs):
+        raise ValueError("one uv triple and one page per face")
+    if len(fcs) and (page.min() < 0 or page.max() >= len(atlases)):
+        raise ValueError("a face on a page without an atlas")
+    if not atlas_ext.startswith(".") or any(c.isspace() for c in os.path.basename(path)):
+        raise ValueError("atlas_ext starts with a dot; the file name holds no white space")
+    stem = os.path.splitext(path)[0]
+    base = os.path.basename(stem)
+    files = [path, stem + ".mtl"]
+    with open(path, "w") as f:
+        f.write(f"# slamhip textured mesh\nmtllib {base}.mtl\n")
+        for p in pts:
+            f.write(f"v {float(p[0])!r} {float(p[1])!r} {float(p[2])!r}\n")
+        for t in uv.reshape(-1, 2):
+            f.write(f"vt {float(t[0])!r} {float(t[1])!r}\n")
+        current = -1
+        for i, t in enumerate(fcs):
+            if page[i] != current:
+                current = int(page[i])
+                f.write(f"usemtl page_{current}\n")
+            f.write(f"f {int(t[0]) + 1}/{3 * i + 1} {int(t[1]) + 1}/{3 * i + 2} {int(t[2]) + 1}/{3 * i + 3}\n")
+    with open(stem + ".mtl", "w") as f:
+        f.write("# slamhip textured mesh\n")
+        for p in range(len(atlases)):
+            f.write(f"newmtl page_{p}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 0\nmap_Kd {base}_atlas_{p}{atlas_ext}\n")
+    for p, a in enumerate(atlases):
+        files.append(f"{stem}_atlas_{p}{atlas_ext}")
+        write_image(files[-1], a, ctx=ctx)
+    return files
+
+
+def load_textured_mesh(path, ctx=None):
+    """write_textured_mesh's own files back: (vertices (n, 3) float64 holding the float32 values of
+    the file, faces (m, 3) int32, uv (m, 3, 2) float64, page (m,) int32, atlases: a list of (h, w, 3)
+    uint8 blue-green-red).  Anything but write_textured_mesh's form raises ValueError."""
+    with open(path) as f:
+        lines = f.read().split("\n")
+    v, vt, fc, pg, mtl, current = [], [], [], [], None, -1
+    for ln in lines:
+        k = ln.split()
+        if not k or k[0] == "#":
+            continue
+        if k[0] == "mtllib" and len(k) == 2:
+            mtl = k[1]
+        elif k[0] == "v" and len(k) == 4:
+            v.append([float(x) for x in k[1:]])
+        elif k[0] == "vt" and len(k) == 3:
+            vt.append([float(x) for x in k[1:]])
+        elif k[0] == "usemtl" and len(k) == 2 and k[1].startswith("page_"):
+            current = int(k[1][5:])
+        elif k[0] == "f" and len(k) == 4:
+            c = [x.split("/") for x in k[1:]]
+            if any(len(x) != 2 for x in c) or [int(x[1]) for x in c] != [3 * len(fc) + 1, 3 * len(fc) + 2, 3 * len(fc) + 3]:
+                raise ValueError(f"{path}: not a mesh written by write_textured_mesh")
+            fc.append([int(x[0]) - 1 for x in c])
+            pg.append(current)
+        else:
+            raise ValueError(f"{path}: not a mesh written by write_textured_mesh")
+    if mtl is None or len(vt) != 3 * len(fc) or (pg and min(pg) < 0):
+        raise ValueError(f"{path}: not a mesh written by write_textured_mesh")
+    maps = {}
+    with open(os.path.join(os.path.dirname(path), mtl)) as f:
+        name = None
+        for ln in f.read().split("\n"):
+            k = ln.split()
+            if k[:1] == ["newmtl"] and len(k) == 2 and k[1].startswith("page_"):
+                name = int(k[1][5:])
+            elif k[:1] == ["map_Kd"] and len(k) == 2 and name is not None:
+                maps[name] = k[1]
+    if sorted(maps) != list(range(len(maps))) or (pg and max(pg) >= len(maps)):
+        raise ValueError(f"{path}: its materials are not write_textured_mesh's")
+    atlases = [read_image(os.path.join(os.path.dirname(path), maps[p]), ctx=ctx) for p in range(len(maps))]
+    return (np.array(v, np.float64).reshape(-1, 3), np.array(fc, np.int32).reshape(-1, 3), np.array(vt, np.float64).reshape(-1, 3, 2),
+            np.array(pg, np.int32).reshape(-1), atlases)
 
 
 
